@@ -14,10 +14,13 @@ dropout 0.1; --deterministic turns them off) — the whole step captured in one 
 the video / mel / waveform trunks on three HIP streams inside the graph.
 Inputs are synthetic, generated on device and resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (value = whole-job clips/s, max step time over ranks).
+Rank 0 prints ONE JSON line (value = whole-job clips/s, max step time over ranks).  A plain run sets up, warms
+up, times the K steps and prints the line.  --dump-outputs DIR then writes what the last timed step returned
+and updated (loss, probabilities, a fixed sample of the parameters) as DIR/<name>.npy.  --full adds the
+measurements that take runs of their own: the isolated-kernel rooflines and the CPU baseline.
 """
 import argparse
 import json
@@ -58,6 +61,10 @@ def parse():
                    help="fp8: bf16 compute with the video trunk's stage-3/4 Linears on MX-fp8 GEMMs (C4's fp8 path)")
     p.add_argument("--eager", action="store_true", help="run the step eagerly instead of replaying its HIP graph")
     p.add_argument("--deterministic", action="store_true", help="regularisers off (the parity setting)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last "
+                   "step's outputs (loss, prob, a seeded sample of the updated parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true", help="also measure the isolated-kernel rooflines and the CPU "
+                   "baseline (the options below apply to these)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-steps", type=int, default=3)
     p.add_argument("--cpu-threads", type=int, default=None, help="torch threads of the CPU baseline (default: every "
@@ -408,6 +415,24 @@ def cpu_baseline(cfg_name, steps, threads=None):
                       f"usable under the cgroup quota ({cores} in the affinity mask)"}
 
 
+PARAM_SAMPLE = 1 << 20   # elements of the flat parameter buffer written by --dump-outputs (4 MiB of fp32)
+
+
+def dump_outputs(path, loss, prob, store):
+    """What the last timed step handed back, as float32 .npy files: the loss (scalar), the probabilities [B] and,
+    since a training step's other result is the updated model, the fp32 master parameters at PARAM_SAMPLE fixed
+    positions of the flat buffer (sorted indices drawn once from a seeded generator: the same positions in every
+    run and every build with the same parameter count)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "prob.npy"), prob.detach().float().reshape(-1).cpu().numpy())
+    n = store.flat.numel()
+    idx = np.sort(np.random.default_rng(20240601).integers(0, n, size=min(PARAM_SAMPLE, n)))
+    sample = store.flat.detach()[torch.from_numpy(idx).to(store.flat.device)]
+    np.save(os.path.join(path, "params_sample.npy"), sample.float().cpu().numpy())
+
+
 def workload_name(name, cfg):
     v = cfg["vst"]
     trunk = "Swin-B" if v["embed_dim"] == 128 else "Swin-T"
@@ -449,14 +474,14 @@ def main():
     feature, label = synthetic_batch(cfg, a.batch, device, 1234 + rank)
 
     for _ in range(max(a.warmup, 1)):
-        loss, _ = step(feature, label)
+        loss, prob = step(feature, label)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss, _ = step(feature, label)
+        loss, prob = step(feature, label)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -469,16 +494,20 @@ def main():
     lossv = float(loss.item())
     clips = world * a.batch * a.steps
     value = clips / el
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, prob, store)
 
+    # the rest takes runs of its own (--full); a plain run reports these fields as null
+    extra = a.full and rank == 0
     # committed counter / trace files describe the C2 bench command only: other configs report none
     c2 = a.config == "c2" and a.batch == 8
-    roof = roofline(cfg, a.batch, dt, a.roofline_iters, pmc=c2) if rank == 0 else None
-    roof_conv = conv3d_roofline(cfg, a.batch, a.roofline_iters, instep=c2) if rank == 0 else None
-    roof_gemm = gemm_roofline(cfg, a.batch, a.roofline_iters, fp8=a.dtype == "fp8") if rank == 0 else None
-    roof_dw = dw_roofline(cfg, a.batch, a.roofline_iters) if rank == 0 else None
-    roof_bwd = attn_bwd_roofline(cfg, a.batch, dt, a.roofline_iters) if rank == 0 else None
+    roof = roofline(cfg, a.batch, dt, a.roofline_iters, pmc=c2) if extra else None
+    roof_conv = conv3d_roofline(cfg, a.batch, a.roofline_iters, instep=c2) if extra else None
+    roof_gemm = gemm_roofline(cfg, a.batch, a.roofline_iters, fp8=a.dtype == "fp8") if extra else None
+    roof_dw = dw_roofline(cfg, a.batch, a.roofline_iters) if extra else None
+    roof_bwd = attn_bwd_roofline(cfg, a.batch, dt, a.roofline_iters) if extra else None
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if extra and world == 1 and not a.no_cpu_baseline:
         try:
             cpu = cpu_baseline(a.config, a.cpu_steps, a.cpu_threads)
         except Exception as e:  # noqa: BLE001 — the baseline must not hide the measured line

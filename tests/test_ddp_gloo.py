@@ -432,8 +432,15 @@ def _fold_worker(rank, world, port, comm, q):
     bk = GradBucketer(store, bucket_mb=0.0002, comm_dtype=comm)
     x, y = _data(1, 8)
     xs, ys = x[rank * 4:(rank + 1) * 4], y[rank * 4:(rank + 1) * 4]
+    # this rank's own gradient, from an identical replica without a bucketer: with fp32 buckets the hooks
+    # all-reduce store.grad in place while backward still runs, so a copy of store.grad taken after backward
+    # holds the local gradient only where a bucket's all-reduce has not yet completed
+    torch.manual_seed(0)
+    m2 = Net()
+    store2 = ParamStore(m2, torch.float32, device=torch.device("cpu"))
+    ((m2(xs) - ys) ** 2).mean().backward()
+    local = store2.grad.clone()
     ((m(xs) - ys) ** 2).mean().backward()
-    local = store.grad.clone()
     fa = bk.finish(fold=True)
     src = fa["grad_bf16"].float() if fa["grad_bf16"] is not None else store.grad
     q.put((rank, local.numpy().copy(), src.numpy().copy(), fa["grad_scale"],

@@ -27,11 +27,11 @@ mkdir -p profiles/r6 && cp $OUT/${TAG}_wattn_fwd_pmc.json profiles/r6/r6_wattn_f
 cp $OUT/${TAG}_conv3d_instep.json profiles/r6/r6_conv3d_instep.json
 CPU=""
 [ "$3" == "skip-cpu" ] && CPU="--no-cpu-baseline"
-timeout -k 10 500 python3 -u bench.py $CPU > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full $CPU > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
 cut -c1-400 $OUT/bench.json
 if [ "$4" == "pe-pmc" ]; then
-  timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $OUT/pe_f -o run --output-format csv -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --roofline-iters 6 > $OUT/pe_f.log 2>&1 || { tail $OUT/pe_f.log; exit 1; }
-  timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE TCC_EA0_WRREQ_sum -d $OUT/pe_w -o run --output-format csv -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --roofline-iters 6 > $OUT/pe_w.log 2>&1 || { tail $OUT/pe_w.log; exit 1; }
+  timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $OUT/pe_f -o run --output-format csv -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --roofline-iters 6 > $OUT/pe_f.log 2>&1 || { tail $OUT/pe_f.log; exit 1; }
+  timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE TCC_EA0_WRREQ_sum -d $OUT/pe_w -o run --output-format csv -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --roofline-iters 6 > $OUT/pe_w.log 2>&1 || { tail $OUT/pe_w.log; exit 1; }
   python3 tools/pe_pmc.py $(find $OUT/pe_f -name run_counter_collection.csv) $(find $OUT/pe_w -name run_counter_collection.csv) > $OUT/${TAG}_conv3d_pmc.txt
   cat $OUT/${TAG}_conv3d_pmc.txt
 fi

@@ -1,4 +1,4 @@
-"""PMC bytes of the fused PatchEmbed3D forward launches of a bench.py run (rocprofv3 --pmc FETCH_SIZE, then
+"""PMC bytes of the fused PatchEmbed3D forward launches of a bench.py --full run (rocprofv3 --pmc FETCH_SIZE, then
 WRITE_SIZE + TCC_EA0_WRREQ_sum): the in-step launches (inside the replayed training step) against the roofline
 loop's cold launches (the last ones), per launch, with the gfx950 correction of FETCH_SIZE (x2 for 16-B-per-lane
 reads, MI355X_MICROARCH.md HBM / rocprofv3 section).  usage: pe_pmc.py fetch.csv write.csv"""
@@ -17,7 +17,7 @@ def rows(path, counter):
 
 def main(fcsv, wcsv):
     f, w, q = rows(fcsv, "FETCH_SIZE"), rows(wcsv, "WRITE_SIZE"), rows(wcsv, "TCC_EA0_WRREQ_sum")
-    # bench.py order: warm-up + timed steps (one launch each; the captured step replays its launch), then the
+    # bench.py --full order: warm-up + timed steps (one launch each; the captured step replays its launch), then the
     # roofline loop (1 + roofline-iters launches): the last 7 are the cold isolated loop
     n_iso = 7
     for name, v in (("FETCH_SIZE KiB", f), ("WRITE_SIZE KiB", w), ("TCC_EA0_WRREQ", q)):
