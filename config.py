@@ -7,6 +7,9 @@
   --train_clips / --val_clips / --test_clips   size of the synthetic split (no media ships with the repo)
   --frames {normalized,uint8}   synthetic frames as the reference's transform output (fp32, ImageNet
                            normalised) or as decoded uint8 RGB frames normalised on the GPU
+  --mel_source {image,uint8,wave,wave16k}   mel slot input: the reference's cached image (fp32 normalised, or
+                           the uint8 grey image), a 22.05 kHz waveform, or the clip's own 16 kHz waveform (the same
+                           samples wav2vec2 gets), resampled and turned into the mel image on the GPU
   --bucket_mb              gradient all-reduce bucket size
   --deterministic          dropout / DropPath / SpecAugment / LayerDrop off (the parity setting, Q12)
   --video_encoder {swin,inception}   video slot: the north-star Video Swin 3D (default) or the reference's
@@ -66,9 +69,10 @@ def build_parser():
     parser.add_argument('--test_clips', type=int, default=16)
     parser.add_argument('--frames', type=str, default='normalized', choices=['normalized', 'uint8'])
     # f2 media front end on the device: mel slot input as the reference's cached image (fp32 normalised or the
-    # uint8 grey image) or as the raw 22.05 kHz waveform (device mel-spectrogram image); train-time frame
-    # augmentation (flips, rotation) of uint8 frames on the device
-    parser.add_argument('--mel_source', type=str, default='image', choices=['image', 'uint8', 'wave'])
+    # uint8 grey image), as the raw 22.05 kHz waveform (device mel-spectrogram image) or as the clip's own 16 kHz
+    # waveform (wave16k: resampled to 22.05 kHz on the device first); train-time frame augmentation (flips,
+    # rotation) of uint8 frames on the device
+    parser.add_argument('--mel_source', type=str, default='image', choices=['image', 'uint8', 'wave', 'wave16k'])
     parser.add_argument('--augment', action='store_true')
     parser.add_argument('--bucket_dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     parser.add_argument('--bucket_mb', type=float, default=64.0)

@@ -10,8 +10,15 @@
 //    overlapping view with row stride = hop, times a window-folded cos | -sin basis); power, filterbank and dB
 //    in mel_power_kernel; per-clip min/max, quantisation and the resize in mel_image_kernel (image in LDS).
 //    The JPEG round trip of the reference's cached images (data_process.py:83-93,162) is not reproduced (a
-//    lossy codec outside the hot path), nor librosa.load's resampling to 22.05 kHz (the caller passes the
-//    waveform at the rate the filterbank was built for).
+//    lossy codec outside the hot path).
+//  * resampling — librosa.load's 16 kHz -> 22.05 kHz step in front of the mel spectrogram (src/utils.py:70):
+//    a polyphase Kaiser-windowed sinc (table built on the host, media.resample_taps; up / down = L / M in lowest
+//    terms), y[n] = sum_j x[i_n + j] H[p_n][j] with n M = i_n L + p_n.  A run of L outputs uses every phase once
+//    and spans M inputs, so a workgroup takes whole periods of one clip, stages their input span plus the filter
+//    halo in LDS and each thread makes one output at a time from LDS.  dfk_resample writes [B][S_out];
+//    dfk_mel_image_resampled lets the same kernel write straight into the centre-padded STFT buffer (in place of
+//    mel_pad_kernel), so the 22.05 kHz waveform makes no round trip of its own.  The filter is this build's
+//    own: parity with librosa's soxr_hq is unpinned.
 //  * gray image -> model input — Image.convert('RGB') + T.ToTensor() + T.Normalize (data_process.py:55-69,162):
 //    uint8 [N, H, W] -> fp32 [N, 3, H, W], (x / 255 - mean[c]) / std[c].
 //  * frame / mel-image transform — torchvision's T.Resize / RandomHorizontalFlip / RandomVerticalFlip /
@@ -29,6 +36,46 @@ __global__ __launch_bounds__(256) void mel_pad_kernel(const float* __restrict__ 
   if (i >= Lp) return;
   const long s = i - half;
   yp[b * Lp + i] = (s >= 0 && s < S) ? y[b * S + s] : 0.f;
+}
+
+// Polyphase resampler.  taps [ntaps][L] in period order: taps[jj][r] = H[(r M) mod L][jj], so the threads of
+// consecutive outputs read consecutive entries.  Workgroup (blockIdx.x, clip blockIdx.y) owns `per` periods:
+// outputs [q0 L, (q0 + per) L) from inputs [q0 M - Z + 1, (q0 + per - 1) M + (M - 1) + Z], Z = ntaps / 2, staged in
+// LDS (zero outside [0, S_in)).  Sample indices are formed per period in 64 bit (n M passes 2^32 on long clips).
+// The output row b starts at y + b ldy + pad; with pad > 0 (the STFT buffer) the first workgroup of each clip
+// also zeroes the pad floats on either side of the S_out samples.
+__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, long S_in,
+                                                       const float* __restrict__ taps, int L, int M, int ntaps,
+                                                       int per, float* __restrict__ y, long S_out, long ldy, int pad) {
+  extern __shared__ float xs[];
+  const long b = blockIdx.y, q0 = (long)blockIdx.x * per;
+  const int span = per * M + ntaps - 1;
+  const long i0 = q0 * M - (ntaps / 2 - 1);
+  const float* xb = x + b * S_in;
+  for (int k = threadIdx.x; k < span; k += blockDim.x) {
+    const long i = i0 + k;
+    xs[k] = (i >= 0 && i < S_in) ? xb[i] : 0.f;
+  }
+  float* yb = y + b * ldy;
+  if (pad > 0 && blockIdx.x == 0) {
+    for (int k = threadIdx.x; k < pad; k += blockDim.x) {
+      yb[k] = 0.f;
+      yb[pad + S_out + k] = 0.f;
+    }
+  }
+  __syncthreads();
+  const long n0 = q0 * L;
+  for (int o = threadIdx.x; o < per * L; o += blockDim.x) {
+    const long n = n0 + o;
+    if (n >= S_out) break;
+    const int qq = o / L, r = o - qq * L;
+    const float* xw = xs + qq * M + (int)(((long)r * M) / L);
+    const float* h = taps + r;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int j = 0; j < ntaps; ++j) acc = fmaf(xw[j], h[(long)j * L], acc);
+    yb[pad + n] = acc;
+  }
 }
 
 // one workgroup per (clip, frame): |X[f]|^2 into LDS, then mel[m] = sum_f fb[m][f] |X[f]|^2 (fp32, the
@@ -234,10 +281,54 @@ extern "C" int64_t dfk_mel_workspace(int64_t B, int64_t S, int32_t n_fft, int32_
   return 4 * (B * Lp + B * T * ldx + B * (long)n_mels * T) + 64;
 }
 
-extern "C" int dfk_mel_image(const float* wave, int64_t B, int64_t S, const float* basis, const float* fbank,
-                             int32_t n_fft, int32_t hop, int32_t n_mels, int32_t out_h, int32_t out_w, void* ws,
-                             int64_t ws_bytes, uint8_t* out, hipStream_t s) {
-  if (!wave || !basis || !fbank || !ws || !out || B <= 0 || S <= 0 || n_fft <= 0 || n_fft % 4 || hop <= 0 ||
+// ceil(S_in up / down), or -1 where it is undefined or does not fit
+static int64_t resample_len(int64_t S_in, int32_t up, int32_t down) {
+  if (S_in <= 0 || up <= 0 || down <= 0 || S_in > (INT64_MAX - down) / up) return -1;
+  return (S_in * up + down - 1) / down;
+}
+
+// periods per workgroup (about 1024 outputs) and the LDS bytes of their input span; 0 where one period's span
+// does not fit the default 64 KB of dynamic LDS
+static int resample_plan(int32_t up, int32_t down, int32_t ntaps, size_t* lds) {
+  const int per = 1024 / up > 1 ? 1024 / up : 1;
+  const long bytes = 4 * ((long)per * down + ntaps);
+  *lds = (size_t)bytes;
+  return bytes <= 64 * 1024 ? per : 0;
+}
+
+static int resample_launch(const float* x, int64_t B, int64_t S_in, const float* taps, int32_t up, int32_t down,
+                           int32_t ntaps, float* y, int64_t S_out, int64_t ldy, int pad, hipStream_t s) {
+  size_t lds;
+  const int per = resample_plan(up, down, ntaps, &lds);
+  const long nblk = (S_out + (long)per * up - 1) / ((long)per * up);
+  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), lds, s, x, (long)S_in, taps, up,
+                     down, ntaps, per, y, (long)S_out, (long)ldy, pad);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+static bool resample_args_ok(const float* x, int64_t B, int64_t S_in, const float* taps, int32_t up, int32_t down,
+                             int32_t ntaps, int64_t S_out) {
+  if (!x || !taps || B <= 0 || B > 65535 || S_in <= 0 || up <= 0 || down <= 0 || ntaps <= 0 || ntaps % 2) return false;
+  if (S_out <= 0 || S_out != resample_len(S_in, up, down)) return false;
+  size_t lds;
+  if (!resample_plan(up, down, ntaps, &lds)) return false;
+  return (S_out + 511) / 512 < (1L << 24);   // a workgroup makes more than 512 outputs: the grid stays below 2^32 threads
+}
+
+extern "C" int dfk_resample(const float* x, int64_t B, int64_t S_in, const float* taps, int32_t up, int32_t down,
+                            int32_t ntaps, float* y, int64_t S_out, hipStream_t s) {
+  if (!y || !resample_args_ok(x, B, S_in, taps, up, down, ntaps, S_out)) return DFK_EINVAL;
+  return resample_launch(x, B, S_in, taps, up, down, ntaps, y, S_out, S_out, 0, s);
+}
+
+// The mel pipeline behind both entry points: argument and LDS-limit checks, `front` fills the centre-padded
+// waveform yp [B][S + n_fft] (S samples at the filterbank's rate), then STFT GEMM, mel power, dB image + resize.
+template <typename Front>
+static int mel_pipeline(int64_t B, int64_t S, const float* basis, const float* fbank, int32_t n_fft, int32_t hop,
+                        int32_t n_mels, int32_t out_h, int32_t out_w, void* ws, int64_t ws_bytes, uint8_t* out,
+                        hipStream_t s, Front front) {
+  if (!basis || !fbank || !ws || !out || B <= 0 || S <= 0 || n_fft <= 0 || n_fft % 4 || hop <= 0 ||
       hop % 4 || n_mels <= 0 || out_h <= 0 || out_w <= 0)
     return DFK_EINVAL;
   if (ws_bytes < dfk_mel_workspace(B, S, n_fft, hop, n_mels)) return DFK_EINVAL;
@@ -246,9 +337,8 @@ extern "C" int dfk_mel_image(const float* wave, int64_t B, int64_t S, const floa
   float* yp = reinterpret_cast<float*>(ws);
   float* X = yp + B * Lp;
   float* Sm = X + B * T * ldx;
-  hipLaunchKernelGGL(mel_pad_kernel, dim3((unsigned)dfk_cdiv(Lp, 256), (unsigned)B), dim3(256), 0, s, wave, (long)S,
-                     n_fft / 2, Lp, yp);
-  DFK_CHECK_LAUNCH();
+  const int rf = front(yp, Lp);
+  if (rf) return rf;
   // STFT: X[b][t][j] = sum_n yp[b][t*hop + n] basis[n][j]  (rows overlap: a strided view with ld = hop)
   dfk_gemm_args g = {};
   g.a.ptr = yp; g.a.ld = hop; g.a.bs0 = Lp;
@@ -272,6 +362,36 @@ extern "C" int dfk_mel_image(const float* wave, int64_t B, int64_t S, const floa
                      out_h, out_w, out);
   DFK_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int dfk_mel_image(const float* wave, int64_t B, int64_t S, const float* basis, const float* fbank,
+                             int32_t n_fft, int32_t hop, int32_t n_mels, int32_t out_h, int32_t out_w, void* ws,
+                             int64_t ws_bytes, uint8_t* out, hipStream_t s) {
+  if (!wave) return DFK_EINVAL;
+  return mel_pipeline(B, S, basis, fbank, n_fft, hop, n_mels, out_h, out_w, ws, ws_bytes, out, s,
+                      [&](float* yp, long Lp) {
+                        hipLaunchKernelGGL(mel_pad_kernel, dim3((unsigned)dfk_cdiv(Lp, 256), (unsigned)B), dim3(256), 0,
+                                           s, wave, (long)S, n_fft / 2, Lp, yp);
+                        DFK_CHECK_LAUNCH();
+                        return 0;
+                      });
+}
+
+extern "C" int64_t dfk_mel_resampled_workspace(int64_t B, int64_t S_in, int32_t up, int32_t down, int32_t n_fft,
+                                               int32_t hop, int32_t n_mels) {
+  const int64_t S = resample_len(S_in, up, down);
+  return S < 0 ? -1 : dfk_mel_workspace(B, S, n_fft, hop, n_mels);
+}
+
+extern "C" int dfk_mel_image_resampled(const float* wave, int64_t B, int64_t S_in, const float* taps, int32_t up,
+                                       int32_t down, int32_t ntaps, int64_t S_out, const float* basis,
+                                       const float* fbank, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t out_h,
+                                       int32_t out_w, void* ws, int64_t ws_bytes, uint8_t* out, hipStream_t s) {
+  if (!resample_args_ok(wave, B, S_in, taps, up, down, ntaps, S_out)) return DFK_EINVAL;
+  return mel_pipeline(B, S_out, basis, fbank, n_fft, hop, n_mels, out_h, out_w, ws, ws_bytes, out, s,
+                      [&](float* yp, long Lp) {
+                        return resample_launch(wave, B, S_in, taps, up, down, ntaps, yp, S_out, Lp, n_fft / 2, s);
+                      });
 }
 
 extern "C" int dfk_gray_normalize(const uint8_t* src, float* dst, int64_t n_img, int32_t H, int32_t W, const float* mean3,

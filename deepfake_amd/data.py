@@ -7,7 +7,10 @@ Items follow DeepFake.__getitem__ (:135-173) with modality 'fused':
   ({"Video": frames, "Audio": mel input, "PAudio": waveform (np.float32, raw)}, label, name)
   mel input: 'image' -> [3,224,224] fp32 (the normalised cached JPEG), 'uint8' -> [224,224] grey image (the
              trainer normalises it on the GPU), 'wave' -> 22.05 kHz waveform (the GPU builds the mel image,
-             deepfake_amd.media, then normalises it)
+             deepfake_amd.media, then normalises it; a draw of its own, unrelated to PAudio), 'wave16k' -> the
+             clip's own 16 kHz waveform, the same samples as PAudio, as the reference builds both audio inputs
+             from one track (src/utils.py:41-49,63-87): the GPU resamples it to 22.05 kHz (librosa.load's step)
+             inside the mel pipeline.  Waveform sources need equal-length clips per batch (Audio is stacked).
   frames: 'normalized' -> [T,3,H,W] fp32, what extract_frames + T.Normalize produce (:55-69, utils.py:22-39)
           'uint8'      -> [T,H,W,3] uint8 decoded RGB frames; the trainer normalises them on the GPU
                           (deepfake_amd.kernels.frame_normalize: ToTensor + Normalize fused)
@@ -60,9 +63,13 @@ class DeepFake(Dataset):
             mel = torch.from_numpy(g.integers(0, 256, size=(224, 224), dtype=np.uint8))
         elif self.mel_source == "wave":      # the waveform librosa.load hands generate_mel_spectrogram (22.05 kHz)
             mel = torch.from_numpy((0.1 * g.standard_normal(int(22050 * self.seconds))).astype(np.float32))
+        elif self.mel_source == "wave16k":   # the clip's one 16 kHz track (extract_wav, src/utils.py:41-49): no mel draw
+            mel = None
         else:
             mel = torch.from_numpy(g.standard_normal((3, 224, 224), dtype=np.float32))
         wave = (0.1 * g.standard_normal(int(16000 * self.seconds))).astype(np.float32)
+        if mel is None:
+            mel = torch.from_numpy(wave.copy())
         feat = {"video": video, "audio": mel, "paudio": wave.copy()}.get(self.modality)
         if self.modality == "fused":
             feat = {"Video": video, "Audio": mel, "PAudio": wave}

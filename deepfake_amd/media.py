@@ -10,7 +10,9 @@ Parity: the frame / mel-image transform follows PIL 12.2 (importable here), as t
 torchvision's transforms to PIL images: pinned bit for bit to PIL fixtures (tests/golden/pil_frames.npz, written
 by tests/golden/make_pil_fixtures.py).  librosa and cv2 are absent, so the mel-spectrogram image stays pinned to
 the restatement in oracle/media.py (librosa 0.10 / OpenCV 4 semantics from their published algorithms) — parity
-unpinned against those libraries."""
+unpinned against those libraries.  The resampling librosa.load applies first (16 kHz -> 22.05 kHz,
+src/utils.py:70) runs here with a filter of this build's own (resample_taps: a stated Kaiser-windowed sinc, held to
+ideal band-limited interpolation); soxr is absent, so parity with soxr_hq is unpinned too."""
 import ctypes
 import functools
 import math
@@ -83,21 +85,90 @@ def _const(key, make, device):
     return t
 
 
-def mel_image(wave, sr=22050, n_fft=2048, hop=512, n_mels=128, size=(224, 224)):
+RESAMPLE_Z, RESAMPLE_BETA = 32, 10.0
+
+
+@functools.lru_cache(maxsize=8)
+def resample_taps(sr_in=16000, sr_out=22050):
+    """The resampler's filter (librosa.load's 16 kHz -> 22.05 kHz step, src/utils.py:70, as this build defines it):
+    (H float32 [L, 2Z], L, M) with L / M = sr_out / sr_in in lowest terms.  A Kaiser-windowed sinc with its cutoff
+    at the input Nyquist, t in input samples,
+        h(t) = sinc(t) I0(beta sqrt(1 - (t / Z)^2)) / I0(beta)  for |t| <= Z, else 0      (Z = 32, beta = 10)
+        H[p][j + Z - 1] = h(p / L - j),  p = 0..L-1,  j = -Z+1..Z,
+    built in float64 and cast to float32.  With x zero outside [0, S_in) and n M = i_n L + p_n (0 <= p_n < L) the
+    resampled signal is y[n] = sum_j x[i_n + j] H[p_n][j + Z - 1], n < ceil(S_in L / M).  Only sr_out >= sr_in."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in <= 0 or sr_out <= 0:
+        raise ValueError("resample_taps: sample rates must be positive")
+    if sr_out < sr_in:
+        raise ValueError("resample_taps: downsampling (sr_out < sr_in) is not built")
+    g = math.gcd(sr_in, sr_out)
+    up, down = sr_out // g, sr_in // g
+    Z = RESAMPLE_Z
+    t = np.arange(up, dtype=np.float64)[:, None] / up - np.arange(-Z + 1, Z + 1, dtype=np.float64)[None, :]
+    win = np.i0(RESAMPLE_BETA * np.sqrt(np.maximum(0.0, 1.0 - (t / Z) ** 2))) / np.i0(RESAMPLE_BETA)
+    h = np.where(np.abs(t) <= Z, np.sinc(t) * win, 0.0)
+    return h.astype(np.float32), up, down
+
+
+def resample_len(S_in, up, down):
+    """ceil(S_in up / down): the length librosa.resample gives."""
+    return -((-int(S_in) * up) // down)
+
+
+def _resample_dev(sr_in, sr_out, device):
+    """(device table, L, M, ntaps); the device copy is [ntaps][L] in period order (output r of a period reads
+    column r: phase (r M) mod L), so consecutive outputs read consecutive entries."""
+    H, up, down = resample_taps(sr_in, sr_out)
+    perm = (np.arange(up) * down) % up
+    taps = _const(("resample", sr_in, sr_out), lambda: np.ascontiguousarray(H[perm].T), device)
+    return taps, up, down, H.shape[1]
+
+
+def resample(wave, sr_in=16000, sr_out=22050):
+    """wave fp32 [B, S_in] (device, at sr_in) -> fp32 [B, ceil(S_in sr_out / sr_in)] at sr_out: the band-limited
+    resampling librosa.load applies before the mel spectrogram (src/utils.py:70), with the filter of
+    resample_taps (parity with soxr_hq unpinned)."""
+    if not wave.is_cuda:
+        raise RuntimeError("resample: device tensors only (no CPU fallback)")
+    x = wave.float().contiguous()
+    B, S = x.shape
+    taps, up, down, ntaps = _resample_dev(int(sr_in), int(sr_out), x.device)
+    S_out = resample_len(S, up, down)
+    y = torch.empty(B, S_out, dtype=torch.float32, device=x.device)
+    L.check(L.lib().dfk_resample(L.ptr(x), B, S, L.ptr(taps), up, down, ntaps, L.ptr(y), S_out, L.stream()),
+            "resample")
+    return y
+
+
+def mel_image(wave, sr=22050, n_fft=2048, hop=512, n_mels=128, size=(224, 224), sr_in=None):
     """wave fp32 [B, S] (device, at `sr`) -> uint8 [B, size[1], size[0]] mel-spectrogram images
-    (generate_mel_spectrogram, src/utils.py:63-87; the reference's fmax argument is unused there)."""
+    (generate_mel_spectrogram, src/utils.py:63-87; the reference's fmax argument is unused there).  sr_in: the
+    rate of `wave` where it differs from `sr` (the clip's own 16 kHz track): resampled to `sr` inside the
+    pipeline (resample's kernel writes the STFT's padded buffer), bit-equal to mel_image(resample(wave))."""
     if not wave.is_cuda:
         raise RuntimeError("mel_image: device tensors only (no CPU fallback)")
     x = wave.float().contiguous()
     B, S = x.shape
     basis = _const(("basis", n_fft), lambda: stft_basis(n_fft), x.device)
     fb = _const(("fb", sr, n_fft, n_mels), lambda: mel_filterbank(sr, n_fft, n_mels), x.device)
+    ow, oh = size
+    out = torch.empty(B, oh, ow, dtype=torch.uint8, device=x.device)
+    if sr_in is not None and int(sr_in) != int(sr):
+        taps, up, down, ntaps = _resample_dev(int(sr_in), int(sr), x.device)
+        S_out = resample_len(S, up, down)
+        nbytes = L.lib().dfk_mel_resampled_workspace(B, S, up, down, n_fft, hop, n_mels)
+        if nbytes < 0:
+            raise RuntimeError("dfk_mel_resampled_workspace: invalid arguments")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        L.check(L.lib().dfk_mel_image_resampled(L.ptr(x), B, S, L.ptr(taps), up, down, ntaps, S_out, L.ptr(basis),
+                                                L.ptr(fb), n_fft, hop, n_mels, oh, ow, L.ptr(ws), nbytes, L.ptr(out),
+                                                L.stream()), "mel_image_resampled")
+        return out
     nbytes = L.lib().dfk_mel_workspace(B, S, n_fft, hop, n_mels)
     if nbytes < 0:
         raise RuntimeError("dfk_mel_workspace: invalid arguments")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    ow, oh = size
-    out = torch.empty(B, oh, ow, dtype=torch.uint8, device=x.device)
     L.check(L.lib().dfk_mel_image(L.ptr(x), B, S, L.ptr(basis), L.ptr(fb), n_fft, hop, n_mels, oh, ow, L.ptr(ws),
                                   nbytes, L.ptr(out), L.stream()), "mel_image")
     return out

@@ -14,6 +14,8 @@ there is no CPU kernel (a CPU tensor raises, as everywhere in the product).  The
 kernels through deepfake_amd.functional, whose direct-gradient protocol (weight gradients accumulated straight
 into the flat gradient buffer) has no torch.library equivalent; these operators are the interface for other
 callers."""
+import math
+
 import torch
 
 from . import _lib as L
@@ -237,6 +239,38 @@ def _(wave, sr=22050, n_fft=2048, hop=512, n_mels=128, out_h=224, out_w=224):
     return wave.new_empty(wave.shape[0], out_h, out_w, dtype=torch.uint8)
 
 
+def _resampled_len(S, sr_in, sr_out):
+    g = math.gcd(sr_in, sr_out)
+    return -((-S * (sr_out // g)) // (sr_in // g))
+
+
+@torch.library.custom_op("dfk::resample", mutates_args=())
+def resample(wave: torch.Tensor, sr_in: int = 16000, sr_out: int = 22050) -> torch.Tensor:
+    """librosa.load's resampling (src/utils.py:70) of a device waveform [B, S]: fp32 [B, ceil(S sr_out / sr_in)]."""
+    _need_gpu(wave)
+    from . import media
+    return media.resample(wave, sr_in, sr_out)
+
+
+@resample.register_fake
+def _(wave, sr_in=16000, sr_out=22050):
+    return wave.new_empty(wave.shape[0], _resampled_len(wave.shape[1], sr_in, sr_out), dtype=torch.float32)
+
+
+@torch.library.custom_op("dfk::mel_image_resampled", mutates_args=())
+def mel_image_resampled(wave: torch.Tensor, sr_in: int = 16000, sr: int = 22050, n_fft: int = 2048, hop: int = 512,
+                        n_mels: int = 128, out_h: int = 224, out_w: int = 224) -> torch.Tensor:
+    """dfk::mel_image from a waveform at sr_in (the clip's own 16 kHz track), resampled to sr inside the pipeline."""
+    _need_gpu(wave)
+    from . import media
+    return media.mel_image(wave, sr, n_fft, hop, n_mels, (out_w, out_h), sr_in=sr_in)
+
+
+@mel_image_resampled.register_fake
+def _(wave, sr_in=16000, sr=22050, n_fft=2048, hop=512, n_mels=128, out_h=224, out_w=224):
+    return wave.new_empty(wave.shape[0], out_h, out_w, dtype=torch.uint8)
+
+
 @torch.library.custom_op("dfk::frame_augment", mutates_args=())
 def frame_augment(frames: torch.Tensor, flips: torch.Tensor | None, angles: torch.Tensor | None, out_h: int = 224,
                   out_w: int = 224) -> torch.Tensor:
@@ -255,4 +289,4 @@ def _(frames, flips, angles, out_h=224, out_w=224):
 
 
 OPS = ("linear", "linear_dx", "linear_dw", "layer_norm", "layer_norm_bwd", "window_attention",
-       "window_attention_bwd", "mel_image", "frame_augment")
+       "window_attention_bwd", "mel_image", "frame_augment", "resample", "mel_image_resampled")

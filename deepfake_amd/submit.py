@@ -5,7 +5,7 @@ the model in eval mode over the test split, probabilities appended to prediction
 'module.' prefix stripped for single-modality checkpoints (:50-74)."""
 import torch
 
-from .trainer import normalize_wave, pad_longest, prepare_video
+from .trainer import mel_sample_rate, normalize_wave, pad_longest, prepare_mel, prepare_video
 from .utils import Logger
 
 
@@ -14,6 +14,7 @@ class SubmitCtl:
         self.device = device
         self.batch_size = args.batch_size
         self.modality = args.modality
+        self.mel_sr = mel_sample_rate(args)
         self.logger = logger or Logger(None)
         self.log_step = args.log_step
         self.model_s = self.model = model.to(device)
@@ -29,14 +30,17 @@ class SubmitCtl:
         self.logger(f"Load Finetuned Model From:{path}")
 
     def _features(self, feat):
+        """As Trainer._features in eval mode: the mel slot goes through prepare_mel without augmentation (the
+        identity for the normalised image; uint8 images and waveforms become the model's input on the device)."""
         if self.modality == "fused":
             wave = normalize_wave(pad_longest(feat["PAudio"]).to(self.device))
-            return (prepare_video(feat["Video"], self.device), feat["Audio"].to(self.device), wave)
+            return (prepare_video(feat["Video"], self.device), prepare_mel(feat["Audio"], self.device, sr=self.mel_sr),
+                    wave)
         if self.modality == "paudio":
             return normalize_wave(pad_longest(feat).to(self.device))
         if self.modality == "video":
             return prepare_video(feat, self.device)
-        return feat.to(self.device)
+        return prepare_mel(feat, self.device, sr=self.mel_sr)
 
     def submit(self, path="prediction.csv"):
         res = {}

@@ -91,16 +91,23 @@ def prepare_video(video, device, augment=False, generator=None, size=224):
     return media.frame_augment(v, (size, size), flips=flips, angles=angles)
 
 
-def prepare_mel(audio, device, augment=False, generator=None, size=224):
+def mel_sample_rate(args):
+    """Rate of a waveform in the mel slot: --mel_source wave16k carries the clip's own 16 kHz track, wave the
+    22.05 kHz signal librosa.load would hand over."""
+    return 16000 if getattr(args, "mel_source", "image") == "wave16k" else 22050
+
+
+def prepare_mel(audio, device, augment=False, generator=None, size=224, sr=22050):
     """The mel slot's input to the device: the normalised image as is; the uint8 grey image (the reference's
-    cached JPEG, data_process.py:162) normalised on the GPU; a raw 22.05 kHz waveform [B, S] turned into the
-    mel-spectrogram image on the GPU first (generate_mel_spectrogram, src/utils.py:63-87).  augment: the
+    cached JPEG, data_process.py:162) normalised on the GPU; a raw waveform [B, S] at `sr` turned into the
+    mel-spectrogram image on the GPU first (generate_mel_spectrogram, src/utils.py:63-87: 22.05 kHz as
+    librosa.load hands it over, or the clip's own 16 kHz track, resampled on the way).  augment: the
     reference runs the mel JPEG through the same self.transform as the frames (data_process.py:162) — in training
     Resize((224, 224)) + flips + RandomRotation(90), one draw per image (media.frame_augment on the grey image)."""
     from . import media
     a = audio.to(device, non_blocking=True)
     if a.dtype != torch.uint8 and a.dim() == 2:
-        a = media.mel_image(a)
+        a = media.mel_image(a, sr_in=sr)
     if a.dtype == torch.uint8:
         if augment:
             n = a.numel() // (a.shape[-2] * a.shape[-1])
@@ -390,6 +397,7 @@ class Trainer:
         self.start_epoch = 0
         self.accum_step = max(1, int(args.accum_step))
         self.augment = bool(getattr(args, "augment", False))
+        self.mel_sr = mel_sample_rate(args)
         self.dataset = dataset
         self.trainloader = dataset.train_dataloader()
         self.valloader = dataset.val_dataloader()
@@ -440,12 +448,13 @@ class Trainer:
         aug = self.augment and self.model.training
         if self.modality == "fused":
             wave = normalize_wave(pad_longest(feat["PAudio"]).to(self.device, non_blocking=True))
-            return (prepare_video(feat["Video"], self.device, aug), prepare_mel(feat["Audio"], self.device, aug), wave)
+            return (prepare_video(feat["Video"], self.device, aug),
+                    prepare_mel(feat["Audio"], self.device, aug, sr=self.mel_sr), wave)
         if self.modality == "paudio":
             return normalize_wave(pad_longest(feat).to(self.device, non_blocking=True))
         if self.modality == "video":
             return prepare_video(feat, self.device, aug)
-        return prepare_mel(feat, self.device, aug)
+        return prepare_mel(feat, self.device, aug, sr=self.mel_sr)
 
     def _prep(self, batch):
         return self._features(batch[0]), batch[1].to(self.device, non_blocking=True)

@@ -438,6 +438,29 @@ int64_t dfk_mel_workspace(int64_t B, int64_t S, int32_t n_fft, int32_t hop, int3
 int dfk_mel_image(const float* wave, int64_t B, int64_t S, const float* basis, const float* fbank, int32_t n_fft,
                   int32_t hop, int32_t n_mels, int32_t out_h, int32_t out_w, void* ws, int64_t ws_bytes, uint8_t* out,
                   hipStream_t stream);
+/* Band-limited resampling in front of the mel spectrogram: librosa.load's 16 kHz -> 22.05 kHz step (src/utils.py:70)
+ * as a polyphase FIR, up / down = sr_out / sr_in in lowest terms (441 / 320).  With x zero outside [0, S_in),
+ *   n down = i_n up + p_n (0 <= p_n < up),   y[n] = sum_{jj < ntaps} x[i_n - ntaps/2 + 1 + jj] H[p_n][jj],
+ * x fp32 [B][S_in] -> y fp32 [B][S_out], S_out = ceil(S_in up / down) (librosa's length).  taps fp32 [ntaps][up] in
+ * period order: taps[jj][r] = H[(r down) mod up][jj], the phase of output r of a period (built by
+ * deepfake_amd.media.resample_taps: a Kaiser-windowed sinc, cutoff at the input Nyquist; the filter is this
+ * build's own, parity with soxr_hq unpinned).  DFK_EINVAL before any launch for null pointers, non-positive
+ * sizes, odd ntaps, S_out != ceil(S_in up / down), B > 65535, or a workgroup's input span (max(1, 1024 / up)
+ * periods of down samples, plus ntaps) beyond 64 KB of LDS. */
+int dfk_resample(const float* x, int64_t B, int64_t S_in, const float* taps, int32_t up, int32_t down, int32_t ntaps,
+                 float* y, int64_t S_out, hipStream_t stream);
+/* generate_mel_spectrogram from the clip's own waveform (src/utils.py:70 librosa.load's resampling, then :63-87):
+ * dfk_mel_image with the resampler in place of the padding copy — the S_out resampled samples are written straight
+ * into the centre-padded STFT buffer, so the waveform at the filterbank's rate makes no round trip of its own;
+ * the output equals dfk_mel_image of dfk_resample's output bit for bit.  wave fp32 [B][S_in]; taps / up / down /
+ * ntaps / S_out as dfk_resample; the rest as dfk_mel_image with S = S_out; ws of dfk_mel_resampled_workspace
+ * bytes (-1 for invalid arguments). */
+int64_t dfk_mel_resampled_workspace(int64_t B, int64_t S_in, int32_t up, int32_t down, int32_t n_fft, int32_t hop,
+                                    int32_t n_mels);
+int dfk_mel_image_resampled(const float* wave, int64_t B, int64_t S_in, const float* taps, int32_t up, int32_t down,
+                            int32_t ntaps, int64_t S_out, const float* basis, const float* fbank, int32_t n_fft,
+                            int32_t hop, int32_t n_mels, int32_t out_h, int32_t out_w, void* ws, int64_t ws_bytes,
+                            uint8_t* out, hipStream_t stream);
 /* Gray uint8 [n, H, W] -> fp32 [n, 3, H, W]: Image.convert('RGB') + T.ToTensor() + T.Normalize(mean, std)
  * (data_process.py:55-69,162); mean3 / std3 are HOST arrays of 3 floats. */
 int dfk_gray_normalize(const uint8_t* src, float* dst, int64_t n_img, int32_t H, int32_t W, const float* mean3,

@@ -1,6 +1,6 @@
 // Host-side checks of libdfk under AddressSanitizer (CPU only; no kernel is launched).  Exercises the C ABI's
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
-// conv0, mel), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
+// conv0, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
 // dims), which must return DFK_EINVAL before touching the device.  Built and run by tools/asan/run.sh.
 #include <cstdio>
 #include <cstring>
@@ -58,10 +58,56 @@ int main() {
   EXPECT(dfk_w2v_conv0_bwd_workspace(8, 64000) > 0);
   EXPECT(dfk_w2v_conv0_fwd_workspace(8, 5) == 0);
   EXPECT(dfk_mel_workspace(8, 88200, 2048, 512, 128) > 0);
+  // resampler in front of the mel pipeline: 4 s at 16 kHz -> 88200 samples at 22.05 kHz, the same plan
+  EXPECT(dfk_mel_resampled_workspace(8, 64000, 441, 320, 2048, 512, 128) > 0);
+  EXPECT(dfk_mel_resampled_workspace(8, 64000, 441, 320, 2048, 512, 128) == dfk_mel_workspace(8, 88200, 2048, 512, 128));
+  EXPECT(dfk_mel_resampled_workspace(8, 0, 441, 320, 2048, 512, 128) == -1);
+  EXPECT(dfk_mel_resampled_workspace(8, 64000, 0, 320, 2048, 512, 128) == -1);
+  EXPECT(dfk_mel_resampled_workspace(8, 64000, 441, -1, 2048, 512, 128) == -1);
+  EXPECT(dfk_mel_resampled_workspace(0, 64000, 441, 320, 2048, 512, 128) == -1);
+  EXPECT(dfk_mel_resampled_workspace(8, INT64_MAX / 2, 441, 320, 2048, 512, 128) == -1);   // S_in * up overflows
+  {
+    const float* fx = reinterpret_cast<const float*>(0x1000);
+    float* fy = reinterpret_cast<float*>(0x2000);
+    void* ws = reinterpret_cast<void*>(0x3000);
+    uint8_t* img = reinterpret_cast<uint8_t*>(0x4000);
+    const int64_t wsb = dfk_mel_resampled_workspace(8, 64000, 441, 320, 2048, 512, 128);
+    // malformed calls return DFK_EINVAL with no launch: null operands, odd ntaps, a wrong S_out, bad sizes
+    EXPECT(dfk_resample(nullptr, 8, 64000, fx, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 64000, nullptr, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 64000, fx, 441, 320, 64, nullptr, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 64000, fx, 441, 320, 63, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 64000, fx, 441, 320, 64, fy, 88199, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 64000, fx, 441, 320, 64, fy, 88201, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 1000, fx, 441, 320, 64, fy, 1378, nullptr) == DFK_EINVAL);   // ceil is 1379
+    EXPECT(dfk_resample(fx, 0, 64000, fx, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 64000, fx, 0, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample(fx, 8, 64000, fx, 441, 320, 0, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(nullptr, 8, 64000, fx, 441, 320, 64, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb,
+                                   img, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(fx, 8, 64000, nullptr, 441, 320, 64, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb,
+                                   img, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(fx, 8, 64000, fx, 441, 320, 64, 88200, nullptr, fx, 2048, 512, 128, 224, 224, ws, wsb,
+                                   img, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(fx, 8, 64000, fx, 441, 320, 64, 88200, fx, nullptr, 2048, 512, 128, 224, 224, ws, wsb,
+                                   img, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(fx, 8, 64000, fx, 441, 320, 64, 88200, fx, fx, 2048, 512, 128, 224, 224, nullptr, wsb,
+                                   img, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(fx, 8, 64000, fx, 441, 320, 64, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb,
+                                   nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(fx, 8, 64000, fx, 441, 320, 64, 88199, fx, fx, 2048, 512, 128, 224, 224, ws, wsb,
+                                   img, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_resampled(fx, 8, 64000, fx, 441, 320, 64, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb - 1,
+                                   img, nullptr) == DFK_EINVAL);
+    // the unchanged 22.05 kHz entry point keeps its checks
+    EXPECT(dfk_mel_image(nullptr, 8, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image(fx, 8, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb - 1, img, nullptr) == DFK_EINVAL);
+  }
   // validation of the other entry points
   EXPECT(dfk_layernorm_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 10, 96, 1e-5f, DFK_BF16, nullptr,
                            nullptr, nullptr) != 0);
-  EXPECT(dfk_sgd_step(nullptr, nullptr, nullptr, nullptr, 10, nullptr, 0.1f, 0.9f, 0.f, 0, nullptr, nullptr) != 0);
+  EXPECT(dfk_sgd_step(nullptr, nullptr, nullptr, nullptr, 10, nullptr, 0.1f, 0.9f, 0.f, 0, nullptr, 1.f, nullptr,
+                      nullptr) != 0);
   EXPECT(dfk_cpb_bias_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 169, 512, 64, nullptr) != 0);
   std::printf("host_check: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);
   return fails ? 1 : 0;
