@@ -10,6 +10,8 @@
   --mel_source {image,uint8,wave,wave16k}   mel slot input: the reference's cached image (fp32 normalised, or
                            the uint8 grey image), a 22.05 kHz waveform, or the clip's own 16 kHz waveform (the same
                            samples wav2vec2 gets), resampled and turned into the mel image on the GPU
+  --audio_seconds_min      shortest synthetic clip (seconds): clips of unequal length, each mel image built from its
+                           clip's own length on the GPU (default: one fixed length)
   --bucket_mb              gradient all-reduce bucket size
   --deterministic          dropout / DropPath / SpecAugment / LayerDrop off (the parity setting, Q12)
   --video_encoder {swin,inception}   video slot: the north-star Video Swin 3D (default) or the reference's
@@ -73,6 +75,10 @@ def build_parser():
     # waveform (wave16k: resampled to 22.05 kHz on the device first); train-time frame augmentation (flips,
     # rotation) of uint8 frames on the device
     parser.add_argument('--mel_source', type=str, default='image', choices=['image', 'uint8', 'wave', 'wave16k'])
+    parser.add_argument('--audio_seconds_min', type=float, default=None,
+                        help='shortest clip in seconds: every clip draws its own audio length between this and the '
+                             "configuration's (unequal clips per batch; the waveform mel sources then build each "
+                             "image from its clip's own length).  Default: every clip has the configuration's length")
     parser.add_argument('--augment', action='store_true')
     parser.add_argument('--bucket_dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     parser.add_argument('--bucket_mb', type=float, default=64.0)
@@ -83,3 +89,14 @@ def build_parser():
 
 def get_opt(argv=None):
     return build_parser().parse_args(argv)
+
+
+def clip_seconds(args, cfg):
+    """The synthetic clips' audio length for deepfake_amd.data.DeepFake: the configuration's fixed length, or with
+    --audio_seconds_min the pair (lo, hi) from which every clip draws its own."""
+    lo = getattr(args, "audio_seconds_min", None)
+    if lo is None:
+        return cfg["seconds"]
+    if not 0 < lo <= cfg["seconds"]:
+        raise ValueError(f"--audio_seconds_min must lie in (0, {cfg['seconds']}], got {lo}")
+    return (lo, cfg["seconds"])

@@ -145,6 +145,9 @@ SIGNATURES = {
     "dfk_mel_resampled_workspace": [_I64, _I64, _I32, _I32, _I32, _I32, _I32],
     "dfk_mel_image_resampled": [_VP, _I64, _I64, _VP, _I32, _I32, _I32, _I64, _VP, _VP, _I32, _I32, _I32, _I32, _I32,
                                 _VP, _I64, _VP, _VP],
+    "dfk_resample_ragged": [_VP, _I64, _I64, _VP, _VP, _I32, _I32, _I32, _VP, _I64, _VP],
+    "dfk_mel_image_ragged": [_VP, _I64, _I64, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _I32, _I32,
+                             _VP, _I64, _VP, _VP],
     "dfk_gray_normalize": [_VP, _VP, _I64, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _VP],
     "dfk_frame_augment": [_VP, _I64, C.POINTER(PilResize), _VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float),
                           _VP, _VP, _VP],

@@ -19,6 +19,9 @@
 //    dfk_mel_image_resampled lets the same kernel write straight into the centre-padded STFT buffer (in place of
 //    mel_pad_kernel), so the 22.05 kHz waveform makes no round trip of its own.  The filter is this build's
 //    own: parity with librosa's soxr_hq is unpinned.
+//  * ragged batches — the reference builds each clip's image from its own track at its own length
+//    (data/data_process.py:82-93): dfk_resample_ragged / dfk_mel_image_ragged take a padded [B][S] batch and a
+//    device array of per-clip lengths, and give every clip what the uniform entry points give it alone.
 //  * gray image -> model input — Image.convert('RGB') + T.ToTensor() + T.Normalize (data_process.py:55-69,162):
 //    uint8 [N, H, W] -> fp32 [N, 3, H, W], (x / 255 - mean[c]) / std[c].
 //  * frame / mel-image transform — torchvision's T.Resize / RandomHorizontalFlip / RandomVerticalFlip /
@@ -29,13 +32,22 @@
 
 namespace {
 
+// Ragged batches (RAGGED kernels below): lengths int64 [B] on the device, clip b holds lengths[b] samples of its
+// row of S, the rest of the row is padding that is never read.  Every kernel clamps the value into [1, S] first, so
+// nothing in that array can take an index outside the row.
+__device__ __forceinline__ long clip_len(const int64_t* __restrict__ lengths, long b, long S) {
+  return (long)min(max(lengths[b], (int64_t)1), (int64_t)S);
+}
+
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void mel_pad_kernel(const float* __restrict__ y, long S, int half, long Lp,
-                                                      float* __restrict__ yp) {
+                                                      float* __restrict__ yp, const int64_t* __restrict__ lengths) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long b = blockIdx.y;
   if (i >= Lp) return;
   const long s = i - half;
-  yp[b * Lp + i] = (s >= 0 && s < S) ? y[b * S + s] : 0.f;
+  const long n = RAGGED ? clip_len(lengths, b, S) : S;
+  yp[b * Lp + i] = (s >= 0 && s < n) ? y[b * S + s] : 0.f;
 }
 
 // Polyphase resampler.  taps [ntaps][L] in period order: taps[jj][r] = H[(r M) mod L][jj], so the threads of
@@ -44,17 +56,24 @@ __global__ __launch_bounds__(256) void mel_pad_kernel(const float* __restrict__ 
 // LDS (zero outside [0, S_in)).  Sample indices are formed per period in 64 bit (n M passes 2^32 on long clips).
 // The output row b starts at y + b ldy + pad; with pad > 0 (the STFT buffer) the first workgroup of each clip
 // also zeroes the pad floats on either side of the S_out samples.
+// RAGGED: the clip ends at n_in = lengths[b] of the row's S_in samples: the staging reads zero from there on,
+// outputs below m = ceil(n_in L / M) are formed exactly as a clip of n_in samples alone would form them, and
+// [m, S_out) is written as zero (workgroups wholly past m write zeros only); the grid covers the row.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, long S_in,
                                                        const float* __restrict__ taps, int L, int M, int ntaps,
-                                                       int per, float* __restrict__ y, long S_out, long ldy, int pad) {
+                                                       int per, float* __restrict__ y, long S_out, long ldy, int pad,
+                                                       const int64_t* __restrict__ lengths) {
   extern __shared__ float xs[];
   const long b = blockIdx.y, q0 = (long)blockIdx.x * per;
+  const long n_in = RAGGED ? clip_len(lengths, b, S_in) : S_in;
+  const long m_out = RAGGED ? (n_in * L + M - 1) / M : S_out;
   const int span = per * M + ntaps - 1;
   const long i0 = q0 * M - (ntaps / 2 - 1);
   const float* xb = x + b * S_in;
   for (int k = threadIdx.x; k < span; k += blockDim.x) {
     const long i = i0 + k;
-    xs[k] = (i >= 0 && i < S_in) ? xb[i] : 0.f;
+    xs[k] = (i >= 0 && i < n_in) ? xb[i] : 0.f;
   }
   float* yb = y + b * ldy;
   if (pad > 0 && blockIdx.x == 0) {
@@ -68,6 +87,10 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
   for (int o = threadIdx.x; o < per * L; o += blockDim.x) {
     const long n = n0 + o;
     if (n >= S_out) break;
+    if (RAGGED && n >= m_out) {
+      yb[pad + n] = 0.f;
+      continue;
+    }
     const int qq = o / L, r = o - qq * L;
     const float* xw = xs + qq * M + (int)(((long)r * M) / L);
     const float* h = taps + r;
@@ -126,22 +149,32 @@ __device__ __forceinline__ void cv_tap(int d, double scale, int sn, int& s0, int
 
 // one workgroup per clip: power_to_db(ref=max, top_db 80), cv2 min-max to [0, 255], uint8 truncation into an
 // LDS image [n_mels][T], then the cv2 fixed-point bilinear resize to [oh][ow]
-__global__ __launch_bounds__(1024) void mel_image_kernel(const float* __restrict__ S, int n_mels, int T, int oh, int ow,
-                                                         uint8_t* __restrict__ out) {
+// RAGGED: S keeps its [n_mels][Tmax] stride, but the clip has only T = 1 + m / hop frames (m = ceil(n_in L / M)
+// samples at the filterbank's rate, n_in = lengths[b] of the row's S_in; L = M = 1 without the resampler).  Frames
+// from T on still overlap the clip's tail, so they are not silent: they are left out of the max, the dB range and
+// the image, which is built [n_mels][T] and resized from T columns, as for a clip of n_in samples alone.
+template <bool RAGGED>
+__global__ __launch_bounds__(1024) void mel_image_kernel(const float* __restrict__ S, int n_mels, int Tmax, int oh,
+                                                         int ow, uint8_t* __restrict__ out,
+                                                         const int64_t* __restrict__ lengths, long S_in, int L, int M,
+                                                         int hop) {
   extern __shared__ uint8_t img[];
   __shared__ float red[16];
   const int b = blockIdx.x;
-  const float* s = S + (long)b * n_mels * T;
+  const float* sb = S + (long)b * n_mels * Tmax;
+  const int T = RAGGED ? min(Tmax, (int)(1 + ((clip_len(lengths, b, S_in) * L + M - 1) / M) / hop)) : Tmax;
   const long n = (long)n_mels * T;
+  // element i of the clip's own [n_mels][T] spectrum (n_mels Tmax fits the LDS image, so 32-bit division does)
+  auto s = [&](long i) { return RAGGED ? sb[((int)i / T) * Tmax + (int)i % T] : sb[i]; };
   float mx = -INFINITY;
-  for (long i = threadIdx.x; i < n; i += blockDim.x) mx = fmaxf(mx, s[i]);
+  for (long i = threadIdx.x; i < n; i += blockDim.x) mx = fmaxf(mx, s(i));
   mx = block_max(mx, red);
   const float amin = 1e-10f;
   const float refdb = 10.f * log10f(fmaxf(amin, mx));
   // dB values, their max (0 up to rounding) and min after the top_db floor
   float dmx = -INFINITY, dmn = INFINITY;
   for (long i = threadIdx.x; i < n; i += blockDim.x) {
-    const float v = 10.f * log10f(fmaxf(amin, s[i])) - refdb;
+    const float v = 10.f * log10f(fmaxf(amin, s(i))) - refdb;
     dmx = fmaxf(dmx, v);
     dmn = fminf(dmn, v);
   }
@@ -152,7 +185,7 @@ __global__ __launch_bounds__(1024) void mel_image_kernel(const float* __restrict
   const double scale = hi > lo ? 255.0 / ((double)hi - (double)lo) : 0.0;
   const double shift = -(double)lo * scale;
   for (long i = threadIdx.x; i < n; i += blockDim.x) {
-    float v = 10.f * log10f(fmaxf(amin, s[i])) - refdb;
+    float v = 10.f * log10f(fmaxf(amin, s(i))) - refdb;
     v = fmaxf(v, floor_db);
     const float q = (float)((double)v * scale + shift);   // cv2 convertTo (double scale / shift), float result
     img[i] = (uint8_t)fminf(fmaxf(q, 0.f), 255.f);        // astype(np.uint8): truncation
@@ -296,13 +329,20 @@ static int resample_plan(int32_t up, int32_t down, int32_t ntaps, size_t* lds) {
   return bytes <= 64 * 1024 ? per : 0;
 }
 
+// lengths: null for whole rows, else the per-clip input lengths of the ragged kernel
 static int resample_launch(const float* x, int64_t B, int64_t S_in, const float* taps, int32_t up, int32_t down,
-                           int32_t ntaps, float* y, int64_t S_out, int64_t ldy, int pad, hipStream_t s) {
+                           int32_t ntaps, float* y, int64_t S_out, int64_t ldy, int pad, hipStream_t s,
+                           const int64_t* lengths = nullptr) {
   size_t lds;
   const int per = resample_plan(up, down, ntaps, &lds);
   const long nblk = (S_out + (long)per * up - 1) / ((long)per * up);
-  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), lds, s, x, (long)S_in, taps, up,
-                     down, ntaps, per, y, (long)S_out, (long)ldy, pad);
+  const dim3 grid((unsigned)nblk, (unsigned)B);
+  if (lengths)
+    hipLaunchKernelGGL(resample_kernel<true>, grid, dim3(256), lds, s, x, (long)S_in, taps, up, down, ntaps, per, y,
+                       (long)S_out, (long)ldy, pad, lengths);
+  else
+    hipLaunchKernelGGL(resample_kernel<false>, grid, dim3(256), lds, s, x, (long)S_in, taps, up, down, ntaps, per, y,
+                       (long)S_out, (long)ldy, pad, lengths);
   DFK_CHECK_LAUNCH();
   return 0;
 }
@@ -322,12 +362,36 @@ extern "C" int dfk_resample(const float* x, int64_t B, int64_t S_in, const float
   return resample_launch(x, B, S_in, taps, up, down, ntaps, y, S_out, S_out, 0, s);
 }
 
-// The mel pipeline behind both entry points: argument and LDS-limit checks, `front` fills the centre-padded
+extern "C" int dfk_resample_ragged(const float* x, int64_t B, int64_t S_in, const int64_t* lengths, const float* taps,
+                                   int32_t up, int32_t down, int32_t ntaps, float* y, int64_t S_out, hipStream_t s) {
+  if (!y || !lengths || !resample_args_ok(x, B, S_in, taps, up, down, ntaps, S_out)) return DFK_EINVAL;
+  return resample_launch(x, B, S_in, taps, up, down, ntaps, y, S_out, S_out, 0, s, lengths);
+}
+
+template <bool RAGGED>
+static void mel_image_launch(const float* Sm, int64_t B, int32_t n_mels, long T, int32_t out_h, int32_t out_w,
+                             uint8_t* out, const int64_t* lengths, int64_t S_in, int32_t up, int32_t down, int32_t hop,
+                             hipStream_t s) {
+  static bool lds_attr = false;   // the uint8 image may take up to 160 KB of dynamic LDS (clips past ~12 s)
+  if (!lds_attr) {
+    // (160 KB minus the kernel's static reduction scratch: the attribute counts dynamic LDS only)
+    (void)hipFuncSetAttribute((const void*)mel_image_kernel<RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024 - 256);
+    lds_attr = true;
+  }
+  hipLaunchKernelGGL(mel_image_kernel<RAGGED>, dim3((unsigned)B), dim3(1024), (size_t)n_mels * T, s, Sm, n_mels,
+                     (int)T, out_h, out_w, out, lengths, (long)S_in, up, down, hop);
+}
+
+// The mel pipeline behind the entry points: argument and LDS-limit checks, `front` fills the centre-padded
 // waveform yp [B][S + n_fft] (S samples at the filterbank's rate), then STFT GEMM, mel power, dB image + resize.
+// lengths (ragged batches, else null): per-clip lengths of rows of S_in samples that up / down take to the
+// filterbank's rate; the STFT and the mel power run over the row's T frames, the image keeps each clip's own.
 template <typename Front>
 static int mel_pipeline(int64_t B, int64_t S, const float* basis, const float* fbank, int32_t n_fft, int32_t hop,
                         int32_t n_mels, int32_t out_h, int32_t out_w, void* ws, int64_t ws_bytes, uint8_t* out,
-                        hipStream_t s, Front front) {
+                        hipStream_t s, Front front, const int64_t* lengths = nullptr, int64_t S_in = 0, int32_t up = 1,
+                        int32_t down = 1) {
   if (!basis || !fbank || !ws || !out || B <= 0 || S <= 0 || n_fft <= 0 || n_fft % 4 || hop <= 0 ||
       hop % 4 || n_mels <= 0 || out_h <= 0 || out_w <= 0)
     return DFK_EINVAL;
@@ -351,15 +415,8 @@ static int mel_pipeline(int64_t B, int64_t S, const float* basis, const float* f
   if (r) return r;
   hipLaunchKernelGGL(mel_power_kernel, dim3((unsigned)T, (unsigned)B), dim3(256), 4 * nbin, s, X, ldx, (int)nbin,
                      (int)T, fbank, n_mels, Sm);
-  static bool lds_attr = false;   // the uint8 image may take up to 160 KB of dynamic LDS (clips past ~12 s)
-  if (!lds_attr) {
-    // (160 KB minus the kernel's static reduction scratch: the attribute counts dynamic LDS only)
-    (void)hipFuncSetAttribute((const void*)mel_image_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 256);
-    lds_attr = true;
-  }
-  hipLaunchKernelGGL(mel_image_kernel, dim3((unsigned)B), dim3(1024), (size_t)n_mels * T, s, Sm, n_mels, (int)T,
-                     out_h, out_w, out);
+  if (lengths) mel_image_launch<true>(Sm, B, n_mels, T, out_h, out_w, out, lengths, S_in, up, down, hop, s);
+  else mel_image_launch<false>(Sm, B, n_mels, T, out_h, out_w, out, nullptr, S, 1, 1, hop, s);
   DFK_CHECK_LAUNCH();
   return 0;
 }
@@ -370,8 +427,8 @@ extern "C" int dfk_mel_image(const float* wave, int64_t B, int64_t S, const floa
   if (!wave) return DFK_EINVAL;
   return mel_pipeline(B, S, basis, fbank, n_fft, hop, n_mels, out_h, out_w, ws, ws_bytes, out, s,
                       [&](float* yp, long Lp) {
-                        hipLaunchKernelGGL(mel_pad_kernel, dim3((unsigned)dfk_cdiv(Lp, 256), (unsigned)B), dim3(256), 0,
-                                           s, wave, (long)S, n_fft / 2, Lp, yp);
+                        hipLaunchKernelGGL(mel_pad_kernel<false>, dim3((unsigned)dfk_cdiv(Lp, 256), (unsigned)B),
+                                           dim3(256), 0, s, wave, (long)S, n_fft / 2, Lp, yp, (const int64_t*)nullptr);
                         DFK_CHECK_LAUNCH();
                         return 0;
                       });
@@ -392,6 +449,33 @@ extern "C" int dfk_mel_image_resampled(const float* wave, int64_t B, int64_t S_i
                       [&](float* yp, long Lp) {
                         return resample_launch(wave, B, S_in, taps, up, down, ntaps, yp, S_out, Lp, n_fft / 2, s);
                       });
+}
+
+extern "C" int dfk_mel_image_ragged(const float* wave, int64_t B, int64_t S, const int64_t* lengths, const float* taps,
+                                    int32_t up, int32_t down, int32_t ntaps, const float* basis, const float* fbank,
+                                    int32_t n_fft, int32_t hop, int32_t n_mels, int32_t out_h, int32_t out_w, void* ws,
+                                    int64_t ws_bytes, uint8_t* out, hipStream_t s) {
+  if (!wave || !lengths || B > 65535) return DFK_EINVAL;
+  if (!taps) {   // plain path: the rows are at the filterbank's rate
+    if (up != 1 || down != 1 || ntaps != 0) return DFK_EINVAL;
+    return mel_pipeline(
+        B, S, basis, fbank, n_fft, hop, n_mels, out_h, out_w, ws, ws_bytes, out, s,
+        [&](float* yp, long Lp) {
+          hipLaunchKernelGGL(mel_pad_kernel<true>, dim3((unsigned)dfk_cdiv(Lp, 256), (unsigned)B), dim3(256), 0, s,
+                             wave, (long)S, n_fft / 2, Lp, yp, lengths);
+          DFK_CHECK_LAUNCH();
+          return 0;
+        },
+        lengths, S, 1, 1);
+  }
+  const int64_t S_out = resample_len(S, up, down);
+  if (!resample_args_ok(wave, B, S, taps, up, down, ntaps, S_out)) return DFK_EINVAL;
+  return mel_pipeline(
+      B, S_out, basis, fbank, n_fft, hop, n_mels, out_h, out_w, ws, ws_bytes, out, s,
+      [&](float* yp, long Lp) {
+        return resample_launch(wave, B, S, taps, up, down, ntaps, yp, S_out, Lp, n_fft / 2, s, lengths);
+      },
+      lengths, S, up, down);
 }
 
 extern "C" int dfk_gray_normalize(const uint8_t* src, float* dst, int64_t n_img, int32_t H, int32_t W, const float* mean3,

@@ -10,12 +10,20 @@ Items follow DeepFake.__getitem__ (:135-173) with modality 'fused':
              deepfake_amd.media, then normalises it; a draw of its own, unrelated to PAudio), 'wave16k' -> the
              clip's own 16 kHz waveform, the same samples as PAudio, as the reference builds both audio inputs
              from one track (src/utils.py:41-49,63-87): the GPU resamples it to 22.05 kHz (librosa.load's step)
-             inside the mel pipeline.  Waveform sources need equal-length clips per batch (Audio is stacked).
+             inside the mel pipeline.  Clips of one length are stacked to [B, S]; clips of unequal length
+             (seconds=(lo, hi)) stay a list of 1-D waveforms, and the trainer pads them and builds every mel
+             image from its clip's own length (deepfake_amd.media.mel_image(..., lengths=)), as the reference
+             builds it per file (data_process.py:82-93).
   frames: 'normalized' -> [T,3,H,W] fp32, what extract_frames + T.Normalize produce (:55-69, utils.py:22-39)
           'uint8'      -> [T,H,W,3] uint8 decoded RGB frames; the trainer normalises them on the GPU
                           (deepfake_amd.kernels.frame_normalize: ToTensor + Normalize fused)
 The test split yields (features, name) like the reference's test set.  Batches are collated by
-fusion_collate / fusion_collate_test (src/utils.py:129-165): Video/Audio stacked, PAudio a list.
+fusion_collate / fusion_collate_test (src/utils.py:129-165): Video/Audio stacked (Audio a list where the items are
+waveforms of unequal length), PAudio a list.
+
+seconds: the clip's audio length; a number (every clip alike) or a pair (lo, hi): the length in 16 kHz samples is
+then drawn per clip from its seeded stream, uniform in [16000 lo, 16000 hi].  The draw is made only for a pair, so
+a fixed length reproduces the clips it always gave.
 """
 import numpy as np
 import torch
@@ -30,7 +38,8 @@ def _rng(seed, index):
 
 
 class DeepFake(Dataset):
-    """Synthetic clips: label ~ Bernoulli(0.5); frames, mel image and waveform from the seeded stream."""
+    """Synthetic clips: label ~ Bernoulli(0.5); frames, mel image and waveform from the seeded stream.
+    seconds: a number, or (lo, hi) for a per-clip length drawn from that stream."""
 
     def __init__(self, args, split="train", n=64, seed=0, frames="normalized", T=None, H=224, W=224, seconds=4,
                  mel_source="image"):
@@ -54,20 +63,36 @@ class DeepFake(Dataset):
         std = torch.tensor(IMAGENET_STD).view(1, 3, 1, 1)
         return x.sub(mean).div(std)                                               # T.Normalize
 
+    def _samples(self, g):
+        """The clip's length in 16 kHz samples: fixed, or for seconds=(lo, hi) one draw from the clip's stream."""
+        if isinstance(self.seconds, (tuple, list)):
+            lo, hi = (int(16000 * float(v)) for v in self.seconds)
+            if not 1 <= lo <= hi:
+                raise ValueError(f"seconds=(lo, hi) needs 1 <= 16000 lo <= 16000 hi, got {self.seconds}")
+            return int(g.integers(lo, hi + 1))
+        return int(16000 * self.seconds)
+
+    def _samples22k(self, n16):
+        """Length of the 22.05 kHz waveform of the 'wave' source for a clip of n16 samples at 16 kHz."""
+        if isinstance(self.seconds, (tuple, list)):
+            return n16 * 22050 // 16000
+        return int(22050 * self.seconds)
+
     def __getitem__(self, index):
         g = _rng(self.seed, index)
         name = f"synthetic_{self.split}_{index:06d}.mp4"
         label = torch.tensor(float(g.uniform() < 0.5), dtype=torch.float32)
         video = self._video(g)
+        n16 = self._samples(g)
         if self.mel_source == "uint8":       # the cached grey JPEG as decoded (data_process.py:83-93,162)
             mel = torch.from_numpy(g.integers(0, 256, size=(224, 224), dtype=np.uint8))
         elif self.mel_source == "wave":      # the waveform librosa.load hands generate_mel_spectrogram (22.05 kHz)
-            mel = torch.from_numpy((0.1 * g.standard_normal(int(22050 * self.seconds))).astype(np.float32))
+            mel = torch.from_numpy((0.1 * g.standard_normal(self._samples22k(n16))).astype(np.float32))
         elif self.mel_source == "wave16k":   # the clip's one 16 kHz track (extract_wav, src/utils.py:41-49): no mel draw
             mel = None
         else:
             mel = torch.from_numpy(g.standard_normal((3, 224, 224), dtype=np.float32))
-        wave = (0.1 * g.standard_normal(int(16000 * self.seconds))).astype(np.float32)
+        wave = (0.1 * g.standard_normal(n16)).astype(np.float32)
         if mel is None:
             mel = torch.from_numpy(wave.copy())
         feat = {"video": video, "audio": mel, "paudio": wave.copy()}.get(self.modality)
@@ -78,10 +103,18 @@ class DeepFake(Dataset):
         return feat, label, name
 
 
+def _stack_audio(items):
+    """The Audio slot of a batch: stacked as the reference stacks it; 1-D waveforms of unequal length stay a list
+    (the trainer pads them and passes their lengths on)."""
+    if all(a.dim() == 1 for a in items) and len({a.shape[0] for a in items}) > 1:
+        return list(items)
+    return torch.stack(items)
+
+
 def fusion_collate(batch):
     """src/utils.py:129-147."""
     features, labels, filenames = zip(*batch)
-    out = {"Video": torch.stack([f["Video"] for f in features]), "Audio": torch.stack([f["Audio"] for f in features]),
+    out = {"Video": torch.stack([f["Video"] for f in features]), "Audio": _stack_audio([f["Audio"] for f in features]),
            "PAudio": [f["PAudio"] for f in features]}
     return out, torch.stack(labels), filenames
 
@@ -89,7 +122,7 @@ def fusion_collate(batch):
 def fusion_collate_test(batch):
     """src/utils.py:149-165."""
     features, filenames = zip(*batch)
-    out = {"Video": torch.stack([f["Video"] for f in features]), "Audio": torch.stack([f["Audio"] for f in features]),
+    out = {"Video": torch.stack([f["Video"] for f in features]), "Audio": _stack_audio([f["Audio"] for f in features]),
            "PAudio": [f["PAudio"] for f in features]}
     return out, filenames
 

@@ -12,7 +12,11 @@ by tests/golden/make_pil_fixtures.py).  librosa and cv2 are absent, so the mel-s
 the restatement in oracle/media.py (librosa 0.10 / OpenCV 4 semantics from their published algorithms) — parity
 unpinned against those libraries.  The resampling librosa.load applies first (16 kHz -> 22.05 kHz,
 src/utils.py:70) runs here with a filter of this build's own (resample_taps: a stated Kaiser-windowed sinc, held to
-ideal band-limited interpolation); soxr is absent, so parity with soxr_hq is unpinned too."""
+ideal band-limited interpolation); soxr is absent, so parity with soxr_hq is unpinned too.
+
+Ragged batches: the reference builds each clip's image from its own track at its own length
+(data/data_process.py:82-93).  resample and mel_image take a padded [B, S] batch with per-clip `lengths` and give
+every clip, bit for bit, what the same call gives that clip alone; the padding is never read."""
 import ctypes
 import functools
 import math
@@ -125,10 +129,37 @@ def _resample_dev(sr_in, sr_out, device):
     return taps, up, down, H.shape[1]
 
 
-def resample(wave, sr_in=16000, sr_out=22050):
+def resample_lengths(lengths, sr_in=16000, sr_out=22050):
+    """Per-clip output lengths of resample(..., lengths=): ceil(n sr_out / sr_in) in exact integers.  A tensor gives
+    an int64 tensor on its own device (no sync, no copy to the host); a sequence of ints gives a list of ints."""
+    g = math.gcd(int(sr_in), int(sr_out))
+    up, down = int(sr_out) // g, int(sr_in) // g
+    if torch.is_tensor(lengths):
+        return torch.div(lengths.to(torch.int64) * up + (down - 1), down, rounding_mode="floor")
+    return [resample_len(n, up, down) for n in lengths]
+
+
+def _clip_lengths(lengths, B, S, what):
+    """lengths of a ragged [B, S] batch as an int64 [B] tensor.  Values on the host (a sequence of ints or a CPU
+    int tensor) are validated here — shape [B], 1 <= n <= S, else ValueError; a device tensor is passed through
+    without reading it (no sync: the kernels clamp every value into [1, S])."""
+    t = lengths if torch.is_tensor(lengths) else torch.as_tensor(list(lengths))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"{what}: lengths must be integers, got {t.dtype}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"{what}: lengths must have shape [{B}] (one per clip), got {list(t.shape)}")
+    if not t.is_cuda and (int(t.min()) < 1 or int(t.max()) > S):
+        raise ValueError(f"{what}: lengths must lie in [1, {S}], got {t.tolist()}")
+    return t.to(torch.int64)
+
+
+def resample(wave, sr_in=16000, sr_out=22050, lengths=None):
     """wave fp32 [B, S_in] (device, at sr_in) -> fp32 [B, ceil(S_in sr_out / sr_in)] at sr_out: the band-limited
     resampling librosa.load applies before the mel spectrogram (src/utils.py:70), with the filter of
-    resample_taps (parity with soxr_hq unpinned)."""
+    resample_taps (parity with soxr_hq unpinned).  lengths (ragged batches, as mel_image's): clip b holds lengths[b]
+    samples of its row; out[b, :m_b] equals resample(wave[b:b+1, :lengths[b]])[0] bit for bit, m_b =
+    resample_lengths(lengths)[b], and out[b, m_b:] is 0.0; the rest of the input row is never read."""
+    n = None if lengths is None else _clip_lengths(lengths, wave.shape[0], wave.shape[-1], "resample")
     if not wave.is_cuda:
         raise RuntimeError("resample: device tensors only (no CPU fallback)")
     x = wave.float().contiguous()
@@ -136,16 +167,30 @@ def resample(wave, sr_in=16000, sr_out=22050):
     taps, up, down, ntaps = _resample_dev(int(sr_in), int(sr_out), x.device)
     S_out = resample_len(S, up, down)
     y = torch.empty(B, S_out, dtype=torch.float32, device=x.device)
+    if n is not None:
+        n = n.to(x.device).contiguous()
+        L.check(L.lib().dfk_resample_ragged(L.ptr(x), B, S, L.ptr(n), L.ptr(taps), up, down, ntaps, L.ptr(y), S_out,
+                                            L.stream()), "resample_ragged")
+        return y
     L.check(L.lib().dfk_resample(L.ptr(x), B, S, L.ptr(taps), up, down, ntaps, L.ptr(y), S_out, L.stream()),
             "resample")
     return y
 
 
-def mel_image(wave, sr=22050, n_fft=2048, hop=512, n_mels=128, size=(224, 224), sr_in=None):
+def mel_image(wave, sr=22050, n_fft=2048, hop=512, n_mels=128, size=(224, 224), sr_in=None, lengths=None):
     """wave fp32 [B, S] (device, at `sr`) -> uint8 [B, size[1], size[0]] mel-spectrogram images
     (generate_mel_spectrogram, src/utils.py:63-87; the reference's fmax argument is unused there).  sr_in: the
     rate of `wave` where it differs from `sr` (the clip's own 16 kHz track): resampled to `sr` inside the
-    pipeline (resample's kernel writes the STFT's padded buffer), bit-equal to mel_image(resample(wave))."""
+    pipeline (resample's kernel writes the STFT's padded buffer), bit-equal to mel_image(resample(wave)).
+
+    lengths: a ragged batch — the reference builds every clip's image from its own track at its own length
+    (data/data_process.py:82-93).  Clip b holds lengths[b] samples (1 <= n <= S) of its row, the rest of the row is
+    padding of any content that is never read, and
+        mel_image(wave, lengths=n, ...)[b] == mel_image(wave[b:b+1, :n[b]].contiguous(), ...)[0]   bit for bit:
+    the dB reference, the min-max stretch and the resized time axis (1 + n_b / hop frames at `sr`) are the clip's
+    own.  A sequence of ints or a CPU int tensor is validated (ValueError); a device int tensor is passed through
+    without a sync and clamped into [1, S] by the kernels.  None: every row is S samples long."""
+    n = None if lengths is None else _clip_lengths(lengths, wave.shape[0], wave.shape[-1], "mel_image")
     if not wave.is_cuda:
         raise RuntimeError("mel_image: device tensors only (no CPU fallback)")
     x = wave.float().contiguous()
@@ -154,6 +199,21 @@ def mel_image(wave, sr=22050, n_fft=2048, hop=512, n_mels=128, size=(224, 224), 
     fb = _const(("fb", sr, n_fft, n_mels), lambda: mel_filterbank(sr, n_fft, n_mels), x.device)
     ow, oh = size
     out = torch.empty(B, oh, ow, dtype=torch.uint8, device=x.device)
+    if n is not None:
+        n = n.to(x.device).contiguous()
+        if sr_in is not None and int(sr_in) != int(sr):
+            taps, up, down, ntaps = _resample_dev(int(sr_in), int(sr), x.device)
+            nbytes = L.lib().dfk_mel_resampled_workspace(B, S, up, down, n_fft, hop, n_mels)
+        else:
+            taps, up, down, ntaps = None, 1, 1, 0
+            nbytes = L.lib().dfk_mel_workspace(B, S, n_fft, hop, n_mels)
+        if nbytes < 0:
+            raise RuntimeError("dfk_mel_workspace: invalid arguments")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        L.check(L.lib().dfk_mel_image_ragged(L.ptr(x), B, S, L.ptr(n), L.ptr(taps), up, down, ntaps, L.ptr(basis),
+                                             L.ptr(fb), n_fft, hop, n_mels, oh, ow, L.ptr(ws), nbytes, L.ptr(out),
+                                             L.stream()), "mel_image_ragged")
+        return out
     if sr_in is not None and int(sr_in) != int(sr):
         taps, up, down, ntaps = _resample_dev(int(sr_in), int(sr), x.device)
         S_out = resample_len(S, up, down)

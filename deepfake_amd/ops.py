@@ -271,6 +271,37 @@ def _(wave, sr_in=16000, sr=22050, n_fft=2048, hop=512, n_mels=128, out_h=224, o
     return wave.new_empty(wave.shape[0], out_h, out_w, dtype=torch.uint8)
 
 
+@torch.library.custom_op("dfk::resample_ragged", mutates_args=())
+def resample_ragged(wave: torch.Tensor, lengths: torch.Tensor, sr_in: int = 16000,
+                    sr_out: int = 22050) -> torch.Tensor:
+    """dfk::resample of a padded batch [B, S] whose clip b holds lengths[b] samples (int tensor [B]): each clip
+    resampled as if alone, zeros past its end."""
+    _need_gpu(wave)
+    from . import media
+    return media.resample(wave, sr_in, sr_out, lengths=lengths)
+
+
+@resample_ragged.register_fake
+def _(wave, lengths, sr_in=16000, sr_out=22050):
+    return wave.new_empty(wave.shape[0], _resampled_len(wave.shape[1], sr_in, sr_out), dtype=torch.float32)
+
+
+@torch.library.custom_op("dfk::mel_image_ragged", mutates_args=())
+def mel_image_ragged(wave: torch.Tensor, lengths: torch.Tensor, sr_in: int = 22050, sr: int = 22050,
+                     n_fft: int = 2048, hop: int = 512, n_mels: int = 128, out_h: int = 224,
+                     out_w: int = 224) -> torch.Tensor:
+    """dfk::mel_image (sr_in == sr) / dfk::mel_image_resampled of a padded batch [B, S] whose clip b holds
+    lengths[b] samples (int tensor [B]): every image built from its clip's own length (data_process.py:82-93)."""
+    _need_gpu(wave)
+    from . import media
+    return media.mel_image(wave, sr, n_fft, hop, n_mels, (out_w, out_h), sr_in=sr_in, lengths=lengths)
+
+
+@mel_image_ragged.register_fake
+def _(wave, lengths, sr_in=22050, sr=22050, n_fft=2048, hop=512, n_mels=128, out_h=224, out_w=224):
+    return wave.new_empty(wave.shape[0], out_h, out_w, dtype=torch.uint8)
+
+
 @torch.library.custom_op("dfk::frame_augment", mutates_args=())
 def frame_augment(frames: torch.Tensor, flips: torch.Tensor | None, angles: torch.Tensor | None, out_h: int = 224,
                   out_w: int = 224) -> torch.Tensor:
@@ -289,4 +320,5 @@ def _(frames, flips, angles, out_h=224, out_w=224):
 
 
 OPS = ("linear", "linear_dx", "linear_dw", "layer_norm", "layer_norm_bwd", "window_attention",
-       "window_attention_bwd", "mel_image", "frame_augment", "resample", "mel_image_resampled")
+       "window_attention_bwd", "mel_image", "frame_augment", "resample", "mel_image_resampled",
+       "resample_ragged", "mel_image_ragged")

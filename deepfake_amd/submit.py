@@ -31,7 +31,8 @@ class SubmitCtl:
 
     def _features(self, feat):
         """As Trainer._features in eval mode: the mel slot goes through prepare_mel without augmentation (the
-        identity for the normalised image; uint8 images and waveforms become the model's input on the device)."""
+        identity for the normalised image; uint8 images and waveforms become the model's input on the device; a
+        list of unequal waveforms takes prepare_mel's ragged path)."""
         if self.modality == "fused":
             wave = normalize_wave(pad_longest(feat["PAudio"]).to(self.device))
             return (prepare_video(feat["Video"], self.device), prepare_mel(feat["Audio"], self.device, sr=self.mel_sr),

@@ -29,16 +29,19 @@ from .params import ParamStore
 from .utils import AverageMeter, Logger
 
 
-def pad_longest(waves):
+def pad_longest(waves, return_lengths=False):
     """The processor's padding='longest' (src/trainer.py:258): zero-pad every waveform of the batch to the
-    longest one -> [B, S] fp32 (host)."""
+    longest one -> [B, S] fp32 (host).  return_lengths: also the clips' own lengths, int64 [B] (host)."""
     if torch.is_tensor(waves):
-        return waves.float()
+        out = waves.float()
+        return (out, torch.full((out.shape[0],), out.shape[-1], dtype=torch.int64)) if return_lengths else out
     arrs = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
     S = max(a.numel() for a in arrs)
     out = torch.zeros(len(arrs), S, dtype=torch.float32)
     for i, a in enumerate(arrs):
         out[i, :a.numel()] = a
+    if return_lengths:
+        return out, torch.tensor([a.numel() for a in arrs], dtype=torch.int64)
     return out
 
 
@@ -97,17 +100,22 @@ def mel_sample_rate(args):
     return 16000 if getattr(args, "mel_source", "image") == "wave16k" else 22050
 
 
-def prepare_mel(audio, device, augment=False, generator=None, size=224, sr=22050):
+def prepare_mel(audio, device, augment=False, generator=None, size=224, sr=22050, lengths=None):
     """The mel slot's input to the device: the normalised image as is; the uint8 grey image (the reference's
     cached JPEG, data_process.py:162) normalised on the GPU; a raw waveform [B, S] at `sr` turned into the
     mel-spectrogram image on the GPU first (generate_mel_spectrogram, src/utils.py:63-87: 22.05 kHz as
-    librosa.load hands it over, or the clip's own 16 kHz track, resampled on the way).  augment: the
-    reference runs the mel JPEG through the same self.transform as the frames (data_process.py:162) — in training
-    Resize((224, 224)) + flips + RandomRotation(90), one draw per image (media.frame_augment on the grey image)."""
+    librosa.load hands it over, or the clip's own 16 kHz track, resampled on the way).  Clips of unequal length
+    come as a list of 1-D waveforms (padded to the longest here) or as a padded [B, S] batch with `lengths`: every
+    image is then built from its clip's own length, as the reference builds it per file (data_process.py:82-93).
+    augment: the reference runs the mel JPEG through the same self.transform as the frames (data_process.py:162)
+    — in training Resize((224, 224)) + flips + RandomRotation(90), one draw per image (media.frame_augment on the
+    grey image)."""
     from . import media
+    if isinstance(audio, (list, tuple)):
+        audio, lengths = pad_longest(audio, return_lengths=True)
     a = audio.to(device, non_blocking=True)
     if a.dtype != torch.uint8 and a.dim() == 2:
-        a = media.mel_image(a, sr_in=sr)
+        a = media.mel_image(a, sr_in=sr, lengths=lengths)
     if a.dtype == torch.uint8:
         if augment:
             n = a.numel() // (a.shape[-2] * a.shape[-1])
@@ -444,7 +452,8 @@ class Trainer:
 
     def _features(self, feat):
         """src/trainer.py:250-262: the batch's features on the device, waveforms padded to the longest and
-        normalised (the processor), frames normalised when they arrive as decoded uint8."""
+        normalised (the processor), frames normalised when they arrive as decoded uint8.  A mel slot that holds
+        a list of unequal waveforms (fusion_collate keeps it one) goes through prepare_mel's ragged path."""
         aug = self.augment and self.model.training
         if self.modality == "fused":
             wave = normalize_wave(pad_longest(feat["PAudio"]).to(self.device, non_blocking=True))

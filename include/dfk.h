@@ -461,6 +461,27 @@ int dfk_mel_image_resampled(const float* wave, int64_t B, int64_t S_in, const fl
                             int32_t ntaps, int64_t S_out, const float* basis, const float* fbank, int32_t n_fft,
                             int32_t hop, int32_t n_mels, int32_t out_h, int32_t out_w, void* ws, int64_t ws_bytes,
                             uint8_t* out, hipStream_t stream);
+/* Ragged batches: the reference builds each clip's mel image from that clip's own track at its own length
+ * (generate_mel_spectrogram, src/utils.py:63-87, called per file at data/data_process.py:82-93), so the dB
+ * reference, the min-max stretch and the resized time axis are per clip.  A batch of unequal clips arrives padded
+ * to rows of S_in samples with lengths int64 [B] on the device (no host read: the call stays capturable); the
+ * kernels clamp every length into [1, S_in] and never read a row past its clip's end, whatever the padding holds.
+ * dfk_resample_ragged: y [B][S_out], S_out = ceil(S_in up / down) of the row as dfk_resample requires; row b equals
+ * dfk_resample of its first lengths[b] samples bit for bit on [0, m_b), m_b = ceil(lengths[b] up / down), and is
+ * 0.0 on [m_b, S_out).  DFK_EINVAL as dfk_resample, and for null lengths. */
+int dfk_resample_ragged(const float* x, int64_t B, int64_t S_in, const int64_t* lengths, const float* taps, int32_t up,
+                        int32_t down, int32_t ntaps, float* y, int64_t S_out, hipStream_t stream);
+/* dfk_mel_image_ragged: out[b] equals, bit for bit, dfk_mel_image (taps == NULL with up = down = 1, ntaps = 0: rows
+ * at the filterbank's rate) or dfk_mel_image_resampled (taps given) of clip b's first lengths[b] samples alone.
+ * The STFT runs over the row's 1 + S_rate / hop frames (S_rate: the row length at the filterbank's rate); the
+ * frames from T_b = 1 + m_b / hop on still overlap the clip's tail and are left out of its image, which is resized
+ * from T_b columns.  ws of dfk_mel_workspace / dfk_mel_resampled_workspace bytes for the row length S.
+ * DFK_EINVAL before any launch for null lengths or operands, taps == NULL with other up / down / ntaps,
+ * B > 65535, or a size the uniform entry points reject. */
+int dfk_mel_image_ragged(const float* wave, int64_t B, int64_t S, const int64_t* lengths, const float* taps, int32_t up,
+                         int32_t down, int32_t ntaps, const float* basis, const float* fbank, int32_t n_fft,
+                         int32_t hop, int32_t n_mels, int32_t out_h, int32_t out_w, void* ws, int64_t ws_bytes,
+                         uint8_t* out, hipStream_t stream);
 /* Gray uint8 [n, H, W] -> fp32 [n, 3, H, W]: Image.convert('RGB') + T.ToTensor() + T.Normalize(mean, std)
  * (data_process.py:55-69,162); mean3 / std3 are HOST arrays of 3 floats. */
 int dfk_gray_normalize(const uint8_t* src, float* dst, int64_t n_img, int32_t H, int32_t W, const float* mean3,

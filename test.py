@@ -14,7 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from config import get_opt  # noqa: E402
+from config import clip_seconds, get_opt  # noqa: E402
 from deepfake_amd.data import DeepFakeSet  # noqa: E402
 from deepfake_amd.models.fused import CONFIGS, build_model  # noqa: E402
 from deepfake_amd.submit import SubmitCtl  # noqa: E402
@@ -25,7 +25,7 @@ def test(args, logger, out_dir="."):
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     model = build_model(args, compute_dtype=dt)
     cfg = CONFIGS[args.config]
-    data = DeepFakeSet(args, logger=logger, clip_shape=dict(T=cfg["T"], H=cfg["H"], W=cfg["W"], seconds=cfg["seconds"]))
+    data = DeepFakeSet(args, logger=logger, clip_shape=dict(T=cfg["T"], H=cfg["H"], W=cfg["W"], seconds=clip_seconds(args, cfg)))
     data.setup(threading.Event())
     device = torch.device("cuda:0")
     tester = SubmitCtl(model, args, device, data, logger)

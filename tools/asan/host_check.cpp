@@ -102,6 +102,58 @@ int main() {
     // the unchanged 22.05 kHz entry point keeps its checks
     EXPECT(dfk_mel_image(nullptr, 8, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img, nullptr) == DFK_EINVAL);
     EXPECT(dfk_mel_image(fx, 8, 88200, fx, fx, 2048, 512, 128, 224, 224, ws, wsb - 1, img, nullptr) == DFK_EINVAL);
+    // ragged batches: null lengths, null operands and every size the uniform entry points reject
+    const int64_t* len = reinterpret_cast<const int64_t*>(0x5000);
+    EXPECT(dfk_resample_ragged(fx, 8, 64000, nullptr, fx, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(nullptr, 8, 64000, len, fx, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(fx, 8, 64000, len, nullptr, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(fx, 8, 64000, len, fx, 441, 320, 64, nullptr, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(fx, 8, 64000, len, fx, 441, 320, 63, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(fx, 8, 64000, len, fx, 441, 320, 64, fy, 88199, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(fx, 8, 1000, len, fx, 441, 320, 64, fy, 1378, nullptr) == DFK_EINVAL);   // ceil is 1379
+    EXPECT(dfk_resample_ragged(fx, 0, 64000, len, fx, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(fx, 65536, 64000, len, fx, 441, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_resample_ragged(fx, 8, 64000, len, fx, 0, 320, 64, fy, 88200, nullptr) == DFK_EINVAL);
+    // resampled path (taps given)
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, nullptr, fx, 441, 320, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(nullptr, 8, 64000, len, fx, 441, 320, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 320, 64, nullptr, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 320, 64, fx, nullptr, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 320, 64, fx, fx, 2048, 512, 128, 224, 224, nullptr, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 320, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, nullptr,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 320, 63, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 0, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 320, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb - 1, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 64000, len, fx, 441, 320, 64, fx, fx, 2046, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 0, len, fx, 441, 320, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 65536, 64000, len, fx, 441, 320, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    // plain path (taps == NULL needs up = down = 1, ntaps = 0; wsb is dfk_mel_workspace(8, 88200, ...))
+    EXPECT(dfk_mel_image_ragged(fx, 8, 88200, nullptr, nullptr, 1, 1, 0, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(nullptr, 8, 88200, len, nullptr, 1, 1, 0, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 88200, len, nullptr, 441, 320, 0, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 88200, len, nullptr, 1, 1, 64, fx, fx, 2048, 512, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 88200, len, nullptr, 1, 1, 0, fx, fx, 2048, 512, 128, 224, 224, ws, wsb - 1, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 88200, len, nullptr, 1, 1, 0, fx, fx, 2048, 510, 128, 224, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
+    EXPECT(dfk_mel_image_ragged(fx, 8, 88200, len, nullptr, 1, 1, 0, fx, fx, 2048, 512, 128, 0, 224, ws, wsb, img,
+                                nullptr) == DFK_EINVAL);
   }
   // validation of the other entry points
   EXPECT(dfk_layernorm_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 10, 96, 1e-5f, DFK_BF16, nullptr,

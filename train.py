@@ -25,7 +25,7 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from config import get_opt  # noqa: E402
+from config import clip_seconds, get_opt  # noqa: E402
 from deepfake_amd.data import DeepFakeSet  # noqa: E402
 from deepfake_amd.models.fused import CONFIGS, build_model  # noqa: E402
 from deepfake_amd.trainer import Trainer  # noqa: E402
@@ -64,9 +64,14 @@ def train(args, logger):
     event = threading.Event()
     atexit.register(shut_sub_prog, event)
     data = DeepFakeSet(args, world_size=world, rank=rank, logger=logger,
-                       clip_shape=dict(T=cfg["T"], H=cfg["H"], W=cfg["W"], seconds=cfg["seconds"]))
+                       clip_shape=dict(T=cfg["T"], H=cfg["H"], W=cfg["W"], seconds=clip_seconds(args, cfg)))
     data.setup(event)
-    trainer = Trainer(model, args, device, data, logger, processor=None, compute_dtype=dt, graph=args.graph)
+    # the captured step's inputs have one shape: clips of unequal length (padded waveforms that change from batch
+    # to batch) run the eager step
+    graph = args.graph and getattr(args, "audio_seconds_min", None) is None
+    if args.graph and not graph:
+        logger("--audio_seconds_min: waveform lengths vary between batches, running the eager step (no HIP graph)")
+    trainer = Trainer(model, args, device, data, logger, processor=None, compute_dtype=dt, graph=graph)
     if args.Resume:
         trainer.load_ckpt(args)
     if not (args.skip_learning or args.val_model):
