@@ -14,6 +14,9 @@
                            clip's own length on the GPU (default: one fixed length)
   --bucket_mb              gradient all-reduce bucket size
   --deterministic          dropout / DropPath / SpecAugment / LayerDrop off (the parity setting, Q12)
+  --optimizer {sgd,adamw}  the reference's SGD(momentum 0.9) (default) or the AdamW it keeps beside it
+                           (src/trainer.py:78: betas (0.9, 0.999), weight decay --l2_decacy), fused on the device;
+                           --adam_beta1, --adam_beta2, --adam_eps set its other hyper-parameters
   --video_encoder {swin,inception}   video slot: the north-star Video Swin 3D (default) or the reference's
                            current InceptionVideoClassifier (Inception-ResNet-v2 + NeXtVLAD, train.py:32,44)
 
@@ -55,7 +58,7 @@ def build_parser():
     parser.add_argument('-e', '--epochs', type=int, default=50, help='input training epoch for training (default: 50)')
     parser.add_argument('-lr', '--learning_rate', type=float, default=1e-4,
                         help='input learning rate for training (default: 1e-4)')
-    parser.add_argument('--model_save', type=int, default=5, help='save model per %d round')
+    parser.add_argument('--model_save', type=int, default=5, help='save model per %%d round')
     parser.add_argument('--skip_learning', action='store_true', help='skip train stage and get submission')
     parser.add_argument('--val_model', action='store_true', help='Eval Model Performence on Eval Set')
     # Log (config.py:43-44)
@@ -84,6 +87,11 @@ def build_parser():
     parser.add_argument('--bucket_mb', type=float, default=64.0)
     parser.add_argument('--deterministic', action='store_true')
     parser.add_argument('--video_encoder', type=str, default='swin', choices=['swin', 'inception'])
+    parser.add_argument('--optimizer', type=str, default='sgd', choices=['sgd', 'adamw'],
+                        help='fused device optimizer: SGD(momentum 0.9) or AdamW, both with --l2_decacy')
+    parser.add_argument('--adam_beta1', type=float, default=0.9)
+    parser.add_argument('--adam_beta2', type=float, default=0.999)
+    parser.add_argument('--adam_eps', type=float, default=1e-8)
     return parser
 
 

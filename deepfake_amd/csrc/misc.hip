@@ -1,7 +1,9 @@
 // Data-movement kernels around the GEMMs: patch im2col (Conv3d/Conv2d with
 // kernel == stride), PatchMerging 2x2 gather / scatter, per-clip row means,
-// dtype casts and the fused SGD step.  All HBM-bound, 16-B vectorised where
+// dtype casts and the fused SGD / AdamW steps.  All HBM-bound, 16-B vectorised where
 // the layout allows.
+#include <math.h>
+
 #include "common.h"
 
 namespace {
@@ -283,6 +285,182 @@ __global__ __launch_bounds__(256) void sgd_runs_kernel(float* __restrict__ P, co
         if (shadow) shadow[i] = f2bf(p[i]);
       }
     }
+  }
+}
+
+// torch.optim.AdamW semantics (amsgrad / maximize off), per element with g = grad * gscale:
+//   p *= 1 - lr*wd ; m = m + (1-b1)(g - m) ; v = b2*v + ((1-b2) g) g ; p -= (lr*c1) m / (sqrt(v)*c2 + eps)
+// c1 = 1/(1-b1^t), c2 = 1/sqrt(1-b2^t) come from adamw_prelude_kernel (evaluated in double, stored fp32, one pair
+// per gate class).  The roundings follow torch's CPU kernels (lerp_ as one fma, addcmul_ as one fma onto the
+// rounded b2*v, then separate multiply / divide / add): an fp32 emulation of this sequence reproduces torch's m and
+// v bit for bit, and p except where the fp32 lr * c1 rounds differently from torch's double lr / (1-b1^t).
+// Contraction is off so that the compiler forms no further fma.
+struct AdamwHyper {
+  float omb1, b2, omb2, eps, wd, gscale;   // 1-b1 and 1-b2 are rounded from double on the host
+};
+
+__device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g, float decay, float step, float c2,
+                                           const AdamwHyper& h) {
+#pragma clang fp contract(off)
+  g = g * h.gscale;
+  p = p * decay;
+  m = __builtin_fmaf(h.omb1, g - m, m);
+  const float vb = v * h.b2;
+  v = __builtin_fmaf(h.omb2 * g, g, vb);
+  const float den = __builtin_sqrtf(v) * c2 + h.eps;
+  p = p - (step * m) / den;
+}
+
+__device__ __forceinline__ float4 ld_grad4(const float* grad, const bf16raw* gbf, long i) {
+  if (gbf) {
+    const uint2 u = *reinterpret_cast<const uint2*>(gbf + i);
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                       __uint_as_float(u.y & 0xffff0000u));
+  }
+  return *reinterpret_cast<const float4*>(grad + i);
+}
+
+// The buffers of one run and its per-step scalars
+struct AdamwRun {
+  float* p;
+  const float* grad;
+  float *m, *v;
+  bf16raw* shadow;
+  const bf16raw* gbf;
+  long n;
+  float decay, step, c2;
+};
+
+struct AdamwQuad {
+  float4 p, g, m, v;
+};
+
+// 4 elements at i (i + 4 <= n): the 16-B loads, then the update and the 16-B stores (8-B for the shadow)
+__device__ __forceinline__ void adamw_load4(const AdamwRun& r, long i, AdamwQuad& q) {
+  q.p = *reinterpret_cast<const float4*>(r.p + i);
+  q.g = ld_grad4(r.grad, r.gbf, i);
+  q.m = *reinterpret_cast<const float4*>(r.m + i);
+  q.v = *reinterpret_cast<const float4*>(r.v + i);
+}
+
+__device__ __forceinline__ void adamw_update4(const AdamwRun& r, long i, AdamwQuad& q, const AdamwHyper& h) {
+  float* pp = reinterpret_cast<float*>(&q.p);
+  const float* gg = reinterpret_cast<const float*>(&q.g);
+  float* mm = reinterpret_cast<float*>(&q.m);
+  float* vq = reinterpret_cast<float*>(&q.v);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) adamw_elem(pp[k], mm[k], vq[k], gg[k], r.decay, r.step, r.c2, h);
+  *reinterpret_cast<float4*>(r.p + i) = q.p;
+  *reinterpret_cast<float4*>(r.m + i) = q.m;
+  *reinterpret_cast<float4*>(r.v + i) = q.v;
+  if (r.shadow) {
+    uint2 w;
+    bf16raw* e = reinterpret_cast<bf16raw*>(&w);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[k] = f2bf(pp[k]);
+    *reinterpret_cast<uint2*>(r.shadow + i) = w;
+  }
+}
+
+// the run's last n - i < 4 elements, one by one
+__device__ __forceinline__ void adamw_tail(const AdamwRun& r, long i, const AdamwHyper& h) {
+  for (; i < r.n; ++i) {
+    float pe = r.p[i], me = r.m[i], ve = r.v[i];
+    adamw_elem(pe, me, ve, r.gbf ? bf2f(r.gbf[i]) : r.grad[i], r.decay, r.step, r.c2, h);
+    r.p[i] = pe;
+    r.m[i] = me;
+    r.v[i] = ve;
+    if (r.shadow) r.shadow[i] = f2bf(pe);
+  }
+}
+
+// Step counts and bias corrections, once per optimizer step ahead of the update kernels: thread i owns class
+// C.cls[i]; unless the class is gated off (*gate == 0) its counter advances, t = ++counters[cls], and
+// corr[2 cls] = 1/(1-b1^t), corr[2 cls + 1] = 1/sqrt(1-b2^t) in double through -expm1(t log b) (1 - 0.999^t formed
+// in fp32 keeps three digits at small t).  A gated-off class keeps its counter and its (unused) corrections.
+constexpr int kAdamwMaxClasses = 64;
+struct AdamwClasses {
+  const float* gate[kAdamwMaxClasses];
+  int32_t cls[kAdamwMaxClasses];
+  int32_t n;
+};
+
+__global__ void adamw_prelude_kernel(int32_t* __restrict__ counters, float* __restrict__ corr, const AdamwClasses C,
+                                     double log_b1, double log_b2) {
+  const int i = threadIdx.x;
+  if (i >= C.n) return;
+  const float* gate = C.gate[i];
+  if (gate && *gate == 0.f) return;
+  const int c = C.cls[i];
+  const int t = counters[c] + 1;
+  counters[c] = t;
+  corr[2 * c] = (float)(1.0 / -expm1((double)t * log_b1));
+  corr[2 * c + 1] = (float)(1.0 / sqrt(-expm1((double)t * log_b2)));
+}
+
+// one run; corr points at its class's {c1, c2}
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ grad, float* __restrict__ m,
+                             float* __restrict__ v, bf16raw* __restrict__ shadow, long n,
+                             const float* __restrict__ lr_dev, float lr_host, const AdamwHyper h,
+                             const float* __restrict__ corr, const float* __restrict__ gate,
+                             const bf16raw* __restrict__ gbf) {
+  const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i0 >= n) return;
+  if (gate && *gate == 0.f) return;   // LayerDrop-skipped layer: torch's AdamW skips grad=None parameters
+  const float lr = lr_dev ? *lr_dev : lr_host;
+  const AdamwRun r{p, grad, m, v, shadow, gbf, n, (float)(1.0 - (double)lr * (double)h.wd), lr * corr[0], corr[1]};
+  if (i0 + 4 <= n) {
+    AdamwQuad q;
+    adamw_load4(r, i0, q);
+    adamw_update4(r, i0, q, h);
+  } else {
+    adamw_tail(r, i0, h);
+  }
+}
+
+// All runs of one step in one launch (dfk_adamw_step_runs), laid out as sgd_runs_kernel: the table by value in the
+// kernel arguments (about 1.9 KB of the 4 KB limit), a workgroup per kSgdRunBlock elements of one run.
+struct AdamwRuns {
+  int64_t start[kSgdMaxRuns], n[kSgdMaxRuns];
+  const float* gate[kSgdMaxRuns];
+  int32_t prefix[kSgdMaxRuns + 1];    // first workgroup of each run; prefix[nruns] = the grid
+  uint8_t cls[kSgdMaxRuns];           // gate class of each run (its pair in corr)
+  int32_t nruns;
+};
+static_assert(sizeof(AdamwRuns) + 128 <= 4096, "run table + the other arguments must fit the kernel-argument block");
+
+__global__ __launch_bounds__(256) void adamw_runs_kernel(float* __restrict__ P, const float* __restrict__ G,
+                                                         float* __restrict__ M, float* __restrict__ V,
+                                                         bf16raw* __restrict__ S, const AdamwRuns R,
+                                                         const float* __restrict__ lr_dev, float lr_host,
+                                                         const AdamwHyper h, const float* __restrict__ corr,
+                                                         const bf16raw* __restrict__ GB) {
+  const int b = blockIdx.x;
+  int lo = 0, hi = R.nruns - 1;                   // the run with prefix[lo] <= b < prefix[lo + 1]
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (R.prefix[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const long start = R.start[lo], n = R.n[lo];
+  const float* gate = R.gate[lo];
+  if (gate && *gate == 0.f) return;
+  const float* cr = corr + 2 * R.cls[lo];
+  const float lr = lr_dev ? *lr_dev : lr_host;
+  const AdamwRun r{P + start, G + start, M + start, V + start, S ? S + start : nullptr, GB ? GB + start : nullptr,
+                   n, (float)(1.0 - (double)lr * (double)h.wd), lr * cr[0], cr[1]};
+  const long base = (long)(b - R.prefix[lo]) * kSgdRunBlock;
+  const long idx[2] = {base + threadIdx.x * 4, base + 1024 + threadIdx.x * 4};
+  AdamwQuad q[2];
+  bool full[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {     // both quads' loads in flight before the first update
+    full[u] = idx[u] + 4 <= n;
+    if (full[u]) adamw_load4(r, idx[u], q[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (full[u]) adamw_update4(r, idx[u], q[u], h);
+    else adamw_tail(r, idx[u], h);       // empty when idx[u] >= n
   }
 }
 
@@ -573,6 +751,90 @@ extern "C" int dfk_sgd_step_runs(float* param, const float* grad, float* momentu
   hipLaunchKernelGGL(sgd_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, momentum_buf,
                      (bf16raw*)bf16_shadow, R, lr_dev, lr, momentum, weight_decay, grad_scale,
                      (const bf16raw*)grad_bf16);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+bool adamw_hyper(double b1, double b2, float eps, float wd, float gscale, AdamwHyper* h) {
+  if (!(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps > 0.f)) return false;
+  *h = AdamwHyper{(float)(1.0 - b1), (float)b2, (float)(1.0 - b2), eps, wd, gscale};
+  return true;
+}
+}  // namespace
+
+extern "C" int dfk_adamw_prelude(int32_t* counters, float* corr, int32_t nclass, const int64_t* classes, int32_t n,
+                                 double b1, double b2, hipStream_t s) {
+  if (!counters || !corr || !classes || nclass <= 0 || n <= 0 || n > nclass) return DFK_EINVAL;
+  if (!(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0)) return DFK_EINVAL;
+  if (nclass > kAdamwMaxClasses) return DFK_ENOTSUP;
+  AdamwClasses C{};
+  C.n = n;
+  for (int i = 0; i < n; ++i) {
+    const int64_t* e = classes + 2 * i;       // {class index, gate pointer}
+    if (e[0] < 0 || e[0] >= nclass) return DFK_EINVAL;
+    for (int j = 0; j < i; ++j)
+      if (C.cls[j] == e[0]) return DFK_EINVAL;   // a class advances once per step
+    C.cls[i] = (int32_t)e[0];
+    C.gate[i] = reinterpret_cast<const float*>(e[1]);
+  }
+  hipLaunchKernelGGL(adamw_prelude_kernel, dim3(1), dim3(kAdamwMaxClasses), 0, s, counters, corr, C, log(b1),
+                     log(b2));
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                              int64_t n, const float* lr_dev, float lr, double b1, double b2, float eps,
+                              float weight_decay, const float* corr, const float* gate, float grad_scale,
+                              const void* grad_bf16, hipStream_t s) {
+  AdamwHyper h;
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !corr) return DFK_EINVAL;
+  if (!adamw_hyper(b1, b2, eps, weight_decay, grad_scale, &h)) return DFK_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+    return DFK_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(grad_bf16) | reinterpret_cast<uintptr_t>(bf16_shadow)) & 7) return DFK_EINVAL;
+  if (n <= 0) return 0;
+  const long threads = (n + 3) / 4;
+  if ((threads + 255) / 256 > 0x7fffffffL) return DFK_EINVAL;
+  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, param, grad, exp_avg,
+                     exp_avg_sq, (bf16raw*)bf16_shadow, (long)n, lr_dev, lr, h, corr, gate,
+                     (const bf16raw*)grad_bf16);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_adamw_step_runs(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                   void* bf16_shadow, const int64_t* runs, int32_t nruns, const float* lr_dev,
+                                   float lr, double b1, double b2, float eps, float weight_decay, const float* corr,
+                                   int32_t nclass, float grad_scale, const void* grad_bf16, hipStream_t s) {
+  AdamwHyper h;
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !corr || !runs || nruns <= 0 || nclass <= 0) return DFK_EINVAL;
+  if (!adamw_hyper(b1, b2, eps, weight_decay, grad_scale, &h)) return DFK_EINVAL;
+  if (nruns > kSgdMaxRuns || nclass > kAdamwMaxClasses) return DFK_ENOTSUP;
+  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+    return DFK_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(grad_bf16) | reinterpret_cast<uintptr_t>(bf16_shadow)) & 7) return DFK_EINVAL;
+  AdamwRuns R{};
+  R.nruns = nruns;
+  int64_t blocks = 0;
+  for (int r = 0; r < nruns; ++r) {
+    const int64_t* e = runs + 4 * r;          // {start, n, gate pointer, class}
+    if (e[1] <= 0 || e[0] < 0 || (e[0] & 3)) return DFK_EINVAL;
+    if (e[3] < 0 || e[3] >= nclass) return DFK_EINVAL;
+    R.start[r] = e[0];
+    R.n[r] = e[1];
+    R.gate[r] = reinterpret_cast<const float*>(e[2]);
+    R.cls[r] = (uint8_t)e[3];
+    R.prefix[r] = (int32_t)blocks;
+    blocks += (e[1] + kSgdRunBlock - 1) / kSgdRunBlock;
+    if (blocks > 0x7fffffffL) return DFK_EINVAL;
+  }
+  R.prefix[nruns] = (int32_t)blocks;
+  hipLaunchKernelGGL(adamw_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq,
+                     (bf16raw*)bf16_shadow, R, lr_dev, lr, h, corr, (const bf16raw*)grad_bf16);
   DFK_CHECK_LAUNCH();
   return 0;
 }

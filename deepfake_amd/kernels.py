@@ -555,6 +555,46 @@ def sgd_step_runs(param, grad, buf, shadow, runs, momentum, wd, lr_dev, grad_sca
                                       L.stream()), "sgd_step_runs")
 
 
+ADAMW_MAX_CLASSES = 64   # dfk_adamw_prelude's by-value class table
+
+
+def adamw_prelude(counters, corr, classes, b1, b2):
+    """Once per optimizer step, before the updates: every class [(index, gate tensor or None)] whose gate is open
+    advances its device step count (int32 counters[index]) and gets its bias corrections in corr[2*index : +2]."""
+    if not 0 < len(classes) <= ADAMW_MAX_CLASSES:
+        raise ValueError(f"adamw_prelude takes 1..{ADAMW_MAX_CLASSES} classes")
+    tab = (ctypes.c_int64 * (2 * len(classes)))(*[v for c, g in classes
+                                                  for v in (c, g.data_ptr() if g is not None else 0)])
+    L.check(L.lib().dfk_adamw_prelude(L.ptr(counters), L.ptr(corr), counters.numel(), tab, len(classes), float(b1),
+                                      float(b2), L.stream()), "adamw_prelude")
+
+
+def adamw_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, b1, b2, eps, wd, corr, lr_dev=None, gate=None,
+               grad_scale=1.0, grad_bf16=None):
+    """One run of the AdamW step; corr: the run's class's fp32 pair written by adamw_prelude."""
+    L.check(L.lib().dfk_adamw_step(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
+                                   L.ptr(shadow) if shadow is not None else None, param.numel(),
+                                   L.ptr(lr_dev) if lr_dev is not None else None, float(lr), float(b1), float(b2),
+                                   float(eps), float(wd), L.ptr(corr), L.ptr(gate), float(grad_scale),
+                                   L.ptr(grad_bf16) if grad_bf16 is not None else None, L.stream()), "adamw_step")
+
+
+def adamw_step_runs(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, wd, lr_dev, corr, grad_scale=1.0,
+                    grad_bf16=None):
+    """Every run [(start, end, gate tensor or None, class index)] of one AdamW step in one launch (same per-element
+    arithmetic as adamw_step); corr: the whole fp32 [2 * classes] table written by adamw_prelude."""
+    if not 0 < len(runs) <= SGD_MAX_RUNS:
+        raise ValueError(f"adamw_step_runs takes 1..{SGD_MAX_RUNS} runs")
+    tab = (ctypes.c_int64 * (4 * len(runs)))(*[v for s, e, g, c in runs
+                                          for v in (s, e - s, g.data_ptr() if g is not None else 0, int(c))])
+    L.check(L.lib().dfk_adamw_step_runs(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
+                                        L.ptr(shadow) if shadow is not None else None, tab, len(runs), L.ptr(lr_dev),
+                                        0.0, float(b1), float(b2), float(eps), float(wd), L.ptr(corr),
+                                        corr.numel() // 2, float(grad_scale),
+                                        L.ptr(grad_bf16) if grad_bf16 is not None else None, L.stream()),
+            "adamw_step_runs")
+
+
 def dropout(x, drop, out=None, group_rows=None):
     """out = x * mask / (1 - p) over a 2-D [rows, cols] view (out may be x)."""
     rows, cols = x.shape

@@ -1,9 +1,12 @@
-"""Fused SGD + CosineAnnealingLR over a ParamStore (src/trainer.py:80-85,295-297).
+"""Fused SGD / AdamW + CosineAnnealingLR over a ParamStore (src/trainer.py:80-85,295-297; AdamW: :6,78).
 
-torch.optim.SGD(lr, momentum=0.9, weight_decay=wd) semantics (dampening 0,
+FusedSGD: torch.optim.SGD(lr, momentum=0.9, weight_decay=wd) semantics (dampening 0,
 no nesterov; first step buf = g) in one HBM-bound kernel over the flat fp32
 buffer, which also rewrites the bf16 compute shadow.  The learning rate lives
 in device memory so a captured graph replays with the scheduler's current lr.
+FusedAdamW: torch.optim.AdamW(betas, eps, weight_decay) in the same form, its
+step counts in device memory too (one per LayerDrop gate class), so a replayed
+graph takes the right bias corrections.
 """
 import math
 import os
@@ -18,6 +21,8 @@ _RUNS = os.environ.get("DFK_SGD_RUNS", "1") != "0"
 
 
 class FusedSGD:
+    folds_grad = True   # step() takes the all-reduced sum and 1 / world itself (TrainStep._fold)
+
     def __init__(self, store, lr, momentum=0.9, weight_decay=0.0):
         self.store = store
         self.base_lr = float(lr)
@@ -67,6 +72,99 @@ class FusedSGD:
 
     def state_dict(self):
         return {"momentum_buffer": self.buf, "lr": self.param_groups[0]["lr"], "first": self.first}
+
+
+class FusedAdamW:
+    """torch.optim.AdamW(lr, betas, eps, weight_decay; amsgrad / maximize off) with FusedSGD's surface.
+
+    Step counts are int32 device memory, one per gate class: class 0 holds the ungated parameters, every distinct
+    LayerDrop flag of ParamStore.gate its own class.  Each step first runs the prelude kernel, which advances the
+    counter of every class whose gate is open and writes its bias corrections, then the update over the runs
+    (dfk_adamw_step_runs; one dfk_adamw_step per run beyond 64 runs).  A gated-off class keeps parameters, moments,
+    shadow and counter, as torch leaves a grad=None parameter, so a layer dropped in step 1 takes t = 1 in step 2."""
+    folds_grad = True
+
+    def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        b1, b2 = float(betas[0]), float(betas[1])
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or not float(eps) > 0.0:
+            raise ValueError(f"FusedAdamW: betas must lie in [0, 1) and eps be positive, got {betas}, {eps}")
+        self.store = store
+        self.base_lr = float(lr)
+        self.betas, self.eps, self.weight_decay = (b1, b2), float(eps), float(weight_decay)
+        dev = store.flat.device
+        self.exp_avg = torch.zeros_like(store.flat)
+        self.exp_avg_sq = torch.zeros_like(store.flat)
+        self.lr_dev = torch.full((1,), self.base_lr, device=dev, dtype=torch.float32)
+        self.param_groups = [{"lr": self.base_lr, "initial_lr": self.base_lr}]
+        self.gates, self.cls, seen = [None], [], {}
+        for g in store.gate:
+            if g is not None and id(g) not in seen:
+                seen[id(g)] = len(self.gates)
+                self.gates.append(g)
+            self.cls.append(0 if g is None else seen[id(g)])
+        if len(self.gates) > K.ADAMW_MAX_CLASSES:
+            raise ValueError(f"FusedAdamW: {len(self.gates)} gate classes, at most {K.ADAMW_MAX_CLASSES}")
+        self.counters = torch.zeros(len(self.gates), device=dev, dtype=torch.int32)
+        self.corr = torch.zeros(2 * len(self.gates), device=dev, dtype=torch.float32)
+        self.active = None   # per parameter: stepped by the eager steps so far (fixed at the first step)
+
+    def set_lr(self, lr):
+        self.param_groups[0]["lr"] = float(lr)
+        self.lr_dev.fill_(float(lr))
+
+    def step(self, first=None, grad_scale=1.0, grad_bf16=None):
+        """One AdamW step over the parameters that received a gradient (all of them without bookkeeping, e.g. under
+        a capture that ran no backward).  `first` is FusedSGD's and ignored: zero moments and the device counters
+        need no first-step flag.  grad_scale / grad_bf16: the data-parallel fold, as FusedSGD.step.
+        The ungated parameters share one counter, so each must be stepped in every step or in none: one whose
+        gradient appears or disappears between steps would need its own count (torch keeps one per parameter)."""
+        st = self.store
+        every = not any(st.touched)
+        touched = [True] * len(st.params) if every else list(st.touched)
+        if self.active is None:
+            self.active = touched
+        for i, (t, a) in enumerate(zip(touched, self.active)):
+            if st.gate[i] is None and t != a:
+                raise RuntimeError(f"FusedAdamW: parameter {st.name(i)} {'received a gradient' if t else 'got none'} "
+                                   f"in this step but {'none' if t else 'one'} before; the ungated parameters "
+                                   f"share one device step count, so its bias correction would be wrong")
+        runs = st.touched_runs(also=self.cls, every=every)
+        if not runs:
+            return
+        b1, b2 = self.betas
+        K.adamw_prelude(self.counters, self.corr, [(c, self.gates[c]) for c in sorted({c for _, _, c in runs})], b1, b2)
+        if len(runs) <= K.SGD_MAX_RUNS:
+            K.adamw_step_runs(st.flat, st.grad, self.exp_avg, self.exp_avg_sq, st.shadow,
+                              [(s, e, self.gates[c], c) for s, e, c in runs], b1, b2, self.eps, self.weight_decay,
+                              self.lr_dev, self.corr, grad_scale=grad_scale, grad_bf16=grad_bf16)
+            return
+        for s, e, c in runs:
+            K.adamw_step(st.flat[s:e], st.grad[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
+                         st.shadow[s:e] if st.shadow is not None else None, 0.0, b1, b2, self.eps, self.weight_decay,
+                         self.corr[2 * c:2 * c + 2], lr_dev=self.lr_dev, gate=self.gates[c], grad_scale=grad_scale,
+                         grad_bf16=grad_bf16[s:e] if grad_bf16 is not None else None)
+
+    def zero_grad(self):
+        self.store.zero_grad()
+
+    def state_dict(self):
+        """The live state (as torch's): moments over the flat store, the per-class device step counts, lr and the
+        hyper-parameters."""
+        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.counters,
+                "lr": self.param_groups[0]["lr"], "base_lr": self.base_lr, "betas": self.betas, "eps": self.eps,
+                "weight_decay": self.weight_decay, "active": self.active}
+
+    def load_state_dict(self, sd):
+        if sd["exp_avg"].numel() != self.exp_avg.numel() or sd["step"].numel() != self.counters.numel():
+            raise ValueError("FusedAdamW.load_state_dict: state of another parameter store")
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self.counters.copy_(sd["step"])
+        self.betas, self.eps = (float(sd["betas"][0]), float(sd["betas"][1])), float(sd["eps"])
+        self.weight_decay, self.base_lr = float(sd["weight_decay"]), float(sd["base_lr"])
+        self.active = list(sd["active"]) if sd["active"] is not None else None
+        self.param_groups[0]["initial_lr"] = self.base_lr
+        self.set_lr(sd["lr"])
 
 
 class CosineAnnealingLR:

@@ -4,7 +4,7 @@ Every trainable fp32 parameter becomes a view into one flat fp32 buffer, its
 ``.grad`` a view into one flat fp32 gradient buffer (so autograd accumulates in
 place and buckets of the flat buffer are all-reduced as-is, no copies), and —
 in bf16 compute mode — a bf16 shadow view (``p._dfk_shadow``) that the GEMMs
-read.  The fused SGD kernel updates the fp32 master and rewrites the shadow in
+read.  The fused optimizer kernel (SGD or AdamW) updates the fp32 master and rewrites the shadow in
 the same pass, so no separate cast kernel runs per step.
 
 Direct mode (default): the HIP backward kernels accumulate weight gradients
@@ -19,7 +19,7 @@ adjacency groups (``flat_groups()``): parameters placed back to back in a given
 order, optionally with zero gaps, so one GEMM reads them as a single operand —
 wav2vec2's q/k/v projections as one [3C, C] weight and [3C] bias, SwinV2's
 (q_bias, 0, v_bias) as the qkv bias — with no per-step concatenation, cast or
-gradient scatter (``group_span``).  Gap elements are never stepped by the SGD.
+gradient scatter (``group_span``).  Gap elements are never stepped by the optimizer.
 """
 import torch
 
@@ -80,11 +80,12 @@ class ParamStore:
                     p._dfk_store = self
                     PARAM_BY_PTR[p.data_ptr()] = p
         self.index = {id(p): i for i, p in enumerate(self.params)}
+        self.names = {id(p): n for n, p in model.named_parameters()}
         self.uses = {}           # id(p) -> forward uses whose backward has not run yet (direct mode)
         self.listeners = []      # callbacks(i) when parameter i's gradient is complete
-        # parameters that received a gradient since the last zero_grad: torch's SGD skips a
+        # parameters that received a gradient since the last zero_grad: torch's optimizers skip a
         # parameter whose .grad is None (no weight decay, no momentum), e.g. Audio2D.classifier
-        # with use_feat=True (Q10) or a LayerDrop-skipped layer; FusedSGD steps only these
+        # with use_feat=True (Q10) or a LayerDrop-skipped layer; FusedSGD / FusedAdamW step only these
         self.touched = [False] * len(self.params)
         for i, p in enumerate(self.params):
             p.register_post_accumulate_grad_hook(self._mark(i))
@@ -181,6 +182,10 @@ class ParamStore:
                 return None
             o += e.numel()
         return start, o - start
+
+    def name(self, i):
+        """Parameter i's name in the model, for messages."""
+        return self.names.get(id(self.params[i]), f"#{i}")
 
     def span(self, i):
         p, o = self.params[i], self.offsets[i]

@@ -6,8 +6,9 @@ re-built MI355X-first:
   overlapped with backward (deepfake_amd.ddp) instead of DataParallel
   (src/trainer.py:74-75);
 * parameters / gradients in flat buffers with a bf16 compute shadow
-  (deepfake_amd.params), fused SGD(momentum 0.9, weight decay) +
-  CosineAnnealingLR (src/trainer.py:80-85) with the lr in device memory;
+  (deepfake_amd.params), fused SGD(momentum 0.9, weight decay), or with
+  --optimizer adamw fused AdamW (src/trainer.py:6,78), + CosineAnnealingLR
+  (src/trainer.py:80-85) with the lr in device memory;
 * BCELoss on the sigmoid output (src/trainer.py:88,132), accuracy
   (prob >= 0.5) == label (:142-144), gradient accumulation over accum_step
   micro-batches with the all-reduce only on the last one (:280-297);
@@ -24,7 +25,7 @@ import torch.distributed as dist
 
 from . import rng
 from .ddp import GradBucketer, fr_last_id, recorder_on
-from .optim import CosineAnnealingLR, FusedSGD
+from .optim import CosineAnnealingLR, FusedAdamW, FusedSGD
 from .params import ParamStore
 from .utils import AverageMeter, Logger
 
@@ -126,14 +127,14 @@ def prepare_mel(audio, device, augment=False, generator=None, size=224, sr=22050
 
 
 class TrainStep:
-    """fwd + BCE + bwd + gradient all-reduce + SGD for one micro-batch, optionally
+    """fwd + BCE + bwd + gradient all-reduce + optimizer step for one micro-batch, optionally
     captured once into a HIP graph and replayed (inputs copied into static buffers).
 
     ``micro(feature, label, last, accum)`` is the gradient-accumulation form of
     src/trainer.py:280-297: loss / accum -> backward for every micro-batch; the
     non-final ones run under the bucketer's no_sync() (no all-reduce), the final
     one launches the overlapped bucket all-reduces over the accumulated sum, then
-    SGD and zero_grad.  BatchNorm running statistics are re-broadcast from rank 0
+    the optimizer step and zero_grad.  BatchNorm running statistics are re-broadcast from rank 0
     at the first micro-step of every optimizer step (§8e)."""
 
     def __init__(self, model, store, opt, bucketer, graph=False, parallel_branches=True):
@@ -180,16 +181,17 @@ class TrainStep:
             return loss.detach(), prob.detach()
         loss, prob = self._fwd_bwd(feature, label, 1.0 / accum)
         fold = self._fold()
-        fa = self.bucketer.finish(fold=fold)   # overlapped bucket all-reduces (hooks); the mean is taken by SGD
-        self.opt.step(**fa)             # first call initialises the momentum buffer (torch SGD semantics)
+        fa = self.bucketer.finish(fold=fold)   # overlapped bucket all-reduces (hooks); the optimizer takes the mean
+        self.opt.step(**fa)             # FusedSGD: the first call initialises the momentum buffer (torch semantics)
         self.store.zero_grad()
         self.first_micro = True
         # detach: a live autograd graph would pin AccumulateGrad nodes to this stream (breaks capture)
         return loss.detach(), prob.detach()
 
     def _fold(self):
-        """The fused SGD kernel takes the all-reduced sum and the 1 / world scale itself (no averaging pass)."""
-        return isinstance(self.opt, FusedSGD)
+        """The fused optimizer kernels take the all-reduced sum and the 1 / world scale themselves (no averaging
+        pass); an optimizer says so with a true `folds_grad` class attribute."""
+        return bool(getattr(self.opt, "folds_grad", False))
 
     def eager(self, feature, label):
         return self._micro_eager(feature, label, True, 1)
@@ -209,9 +211,9 @@ class TrainStep:
 
     def _micro_graphed(self, feature, label, last, accum):
         """Gradient accumulation with graphs (src/trainer.py:280-297 at --accum_step > 1): the non-final micro-step
-        (fwd + bwd of loss / accum under no_sync) and the final one (the same, then the bucket all-reduces, SGD and
-        the gradient zeroing that opens the next window) are captured as two graphs after one eager window, and
-        each micro-step replays one of them.  BatchNorm statistics are broadcast eagerly at each window's start."""
+        (fwd + bwd of loss / accum under no_sync) and the final one (the same, then the bucket all-reduces, the
+        optimizer step and the gradient zeroing that opens the next window) are captured as two graphs after one eager
+        window, and each micro-step replays one of them.  BatchNorm statistics are broadcast eagerly at each window's start."""
         if self.agraphs is None:
             loss, prob = self._micro_eager(feature, label, last, accum)
             if last:
@@ -311,7 +313,7 @@ class TrainStep:
         return g, outs
 
     def _step_body(self, static_in, static_label, accum):
-        """The optimizer step's graph body: (zeroing,) BN broadcast, fwd + bwd, all-reduces, SGD."""
+        """The optimizer step's graph body: (zeroing,) BN broadcast, fwd + bwd, all-reduces, optimizer."""
         # where the step graph zeroes the gradients (A/B): 0 at the start, 1 after the forward, 2 on a side stream
         # beside the forward (joined before the backward)
         zmode = int(os.environ.get("DFK_ZERO_MODE", "0")) if accum == 1 else 0
@@ -356,7 +358,8 @@ class TrainStep:
         self.store.zero_grad()
 
     def _capture_step(self, feature, label):
-        """Capture the whole step — grad zeroing, BN broadcast, fwd, bwd, bucket all-reduces, SGD — as one graph.
+        """Capture the whole step — grad zeroing, BN broadcast, fwd, bwd, bucket all-reduces, optimizer — as one
+        graph.
         Multi-GPU: the bucket all-reduces are captured where the backward completes each bucket (on the comm
         stream, overlapping the rest of backward, §8e); if any rank cannot capture that form, every rank retries
         with one all-reduce pass after backward, then with the BN broadcast outside the graph, and only then do
@@ -424,7 +427,12 @@ class Trainer:
         if self.bucketer.enabled:                      # identical replicas: parameters from rank 0
             dist.broadcast(self.store.flat, 0)
             self.store.refresh_shadow()
-        self.optimizer = FusedSGD(self.store, args.learning_rate, momentum=0.9, weight_decay=args.l2_decacy)
+        if getattr(args, "optimizer", "sgd") == "adamw":   # src/trainer.py:78
+            self.optimizer = FusedAdamW(self.store, args.learning_rate,
+                                        betas=(getattr(args, "adam_beta1", 0.9), getattr(args, "adam_beta2", 0.999)),
+                                        eps=getattr(args, "adam_eps", 1e-8), weight_decay=args.l2_decacy)
+        else:
+            self.optimizer = FusedSGD(self.store, args.learning_rate, momentum=0.9, weight_decay=args.l2_decacy)
         steps_per_epoch = max(1, int(len(self.trainloader) / self.accum_step))
         self.scheduler = CosineAnnealingLR(self.optimizer, T_max=self.train_epochs * steps_per_epoch)
         self.step_fn = TrainStep(model, self.store, self.optimizer, self.bucketer, graph=graph)

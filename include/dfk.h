@@ -386,6 +386,33 @@ int dfk_sgd_step_runs(float* param, const float* grad, float* momentum_buf, void
  * DataParallel's averaging of src/trainer.py:74-75 folded into the step); grad_bf16 (NULL, or 8-B aligned):
  * read the gradient from this bf16 buffer (the all-reduced bf16 bucket copy) instead of `grad`. */
 
+/* torch.optim.AdamW(betas, eps, weight_decay; amsgrad and maximize off) over the same flat store — the optimizer
+ * the reference imports at src/trainer.py:6 and keeps ready at src/trainer.py:78 beside the SGD it runs.  Per element,
+ * g = grad * grad_scale:  p *= 1 - lr*wd;  m += (1-b1)(g - m);  v = b2 v + (1-b2) g g;
+ * p -= lr c1 m / (sqrt(v) c2 + eps);  shadow = bf16(p).  exp_avg / exp_avg_sq start at zero.  b1, b2 are doubles:
+ * 1 - b2 taken from a float 0.999 is off by 1e-5 relative.  lr_dev, gate, grad_scale, grad_bf16 and the alignment
+ * rules are dfk_sgd_step's; DFK_EINVAL also for b1, b2 outside [0, 1) and eps <= 0.
+ * Step counts live in device memory, one int32 per gate class (class = the parameters sharing one gate flag, plus
+ * one class for the ungated ones), so a replayed graph advances them.  dfk_adamw_prelude runs once per optimizer
+ * step, before the update launches: for each listed class whose gate is NULL or *gate != 0, t = ++counters[class],
+ * corr[2 class] = c1 = 1/(1-b1^t) and corr[2 class + 1] = c2 = 1/sqrt(1-b2^t), evaluated in double as
+ * -expm1(t log b) and stored fp32; a gated-off class keeps its counter.  classes: HOST int64 [n][2] = {class index
+ * < nclass, gate device pointer (0: none)}, each class at most once, copied into the launch arguments; nclass <= 64
+ * (DFK_ENOTSUP beyond).  counters: int32 [nclass], corr: fp32 [2 nclass], both device. */
+int dfk_adamw_prelude(int32_t* counters, float* corr, int32_t nclass, const int64_t* classes, int32_t n, double b1,
+                      double b2, hipStream_t stream);
+/* One run; corr points at the {c1, c2} pair of the run's class. */
+int dfk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow, int64_t n,
+                   const float* lr_dev, float lr, double b1, double b2, float eps, float weight_decay,
+                   const float* corr, const float* gate, float grad_scale, const void* grad_bf16, hipStream_t stream);
+/* Every run of the step in one launch, as dfk_sgd_step_runs: runs HOST int64 [nruns][4] = {start element, n, gate
+ * device pointer (0: none), class index < nclass}; nruns <= 64 (DFK_ENOTSUP beyond: the caller loops
+ * dfk_adamw_step); corr is the whole fp32 [2 nclass] table. */
+int dfk_adamw_step_runs(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                        const int64_t* runs, int32_t nruns, const float* lr_dev, float lr, double b1, double b2,
+                        float eps, float weight_decay, const float* corr, int32_t nclass, float grad_scale,
+                        const void* grad_bf16, hipStream_t stream);
+
 /* y = x * mask / (1 - p) over [rows, cols] (row stride ld; y may alias x): nn.Dropout / DropPath as a
  * standalone pass, and the backward of every fused dropout site (the same mask applied to the gradient). */
 int dfk_dropout(const void* x, void* y, int64_t rows, int32_t cols, int64_t ld, const dfk_drop* drop, int dtype,

@@ -1,7 +1,8 @@
 // Host-side checks of libdfk under AddressSanitizer (CPU only; no kernel is launched).  Exercises the C ABI's
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
 // conv0, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
-// dims), which must return DFK_EINVAL before touching the device.  Built and run by tools/asan/run.sh.
+// dims, the AdamW entry points' buffers / run table / hyper-parameters), which must return DFK_EINVAL before touching
+// the device.  Built and run by tools/asan/run.sh.
 #include <cstdio>
 #include <cstring>
 
@@ -160,6 +161,75 @@ int main() {
                            nullptr, nullptr) != 0);
   EXPECT(dfk_sgd_step(nullptr, nullptr, nullptr, nullptr, 10, nullptr, 0.1f, 0.9f, 0.f, 0, nullptr, 1.f, nullptr,
                       nullptr) != 0);
+  {
+    // AdamW: malformed calls return before any launch (fx: a fake 16-B aligned device pointer, never touched)
+    float* fx = reinterpret_cast<float*>(0x10000);
+    float* odd = reinterpret_cast<float*>(0x10004);
+    int32_t* cnt = reinterpret_cast<int32_t*>(0x20000);
+    EXPECT(dfk_adamw_step(nullptr, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step(fx, nullptr, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step(fx, fx, nullptr, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step(fx, fx, fx, nullptr, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step(fx, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, nullptr, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);                         // no corrections
+    EXPECT(dfk_adamw_step(odd, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);                         // misaligned parameter
+    EXPECT(dfk_adamw_step(fx, fx, fx, odd, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);                         // misaligned exp_avg_sq
+    EXPECT(dfk_adamw_step(fx, fx, fx, fx, odd, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);                         // shadow not 8-B aligned
+    EXPECT(dfk_adamw_step(fx, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, odd,
+                          nullptr) == DFK_EINVAL);                         // grad_bf16 not 8-B aligned
+    EXPECT(dfk_adamw_step(fx, fx, fx, fx, nullptr, 16, fx, 0.f, 1.0, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);                         // b1 = 1
+    EXPECT(dfk_adamw_step(fx, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, -0.1, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);                         // b2 < 0
+    EXPECT(dfk_adamw_step(fx, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 0.f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == DFK_EINVAL);                         // eps = 0
+    EXPECT(dfk_adamw_step(fx, fx, fx, fx, nullptr, -4, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                          nullptr) == 0);                                  // n <= 0: nothing to do, as dfk_sgd_step
+    int64_t runs[65 * 4];
+    for (int r = 0; r < 65; ++r) { runs[4 * r] = 64 * r; runs[4 * r + 1] = 40; runs[4 * r + 2] = 0; runs[4 * r + 3] = 0; }
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 0, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f, nullptr,
+                               nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 65, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f, nullptr,
+                               nullptr) == DFK_ENOTSUP);
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, nullptr, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
+                               nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs(nullptr, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
+                               nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs(fx, fx, odd, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
+                               nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 1.5, 1e-8f, 0.f, fx, 1, 1.f, nullptr,
+                               nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, -1.f, 0.f, fx, 1, 1.f, nullptr,
+                               nullptr) == DFK_EINVAL);
+    runs[4] = 66;                                                          // run start not a multiple of 4
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f, nullptr,
+                               nullptr) == DFK_EINVAL);
+    runs[4] = 64; runs[5] = -8;                                            // negative n
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f, nullptr,
+                               nullptr) == DFK_EINVAL);
+    runs[5] = 40; runs[7] = 1;                                             // class index beyond nclass
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f, nullptr,
+                               nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 65, 1.f, nullptr,
+                               nullptr) == DFK_ENOTSUP);
+    int64_t cls[6] = {0, 0, 1, 0, 1, 0};
+    EXPECT(dfk_adamw_prelude(nullptr, fx, 2, cls, 2, 0.9, 0.999, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_prelude(cnt, nullptr, 2, cls, 2, 0.9, 0.999, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_prelude(cnt, fx, 2, nullptr, 2, 0.9, 0.999, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_prelude(cnt, fx, 2, cls, 0, 0.9, 0.999, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_prelude(cnt, fx, 2, cls, 3, 0.9, 0.999, nullptr) == DFK_EINVAL);   // more entries than classes
+    EXPECT(dfk_adamw_prelude(cnt, fx, 1, cls, 1, 0.9, 1.0, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_prelude(cnt, fx, 1, cls + 2, 1, 0.9, 0.999, nullptr) == DFK_EINVAL);   // class 1 of 1
+    EXPECT(dfk_adamw_prelude(cnt, fx, 3, cls + 2, 2, 0.9, 0.999, nullptr) == DFK_EINVAL);   // class 1 listed twice
+    EXPECT(dfk_adamw_prelude(cnt, fx, 65, cls, 2, 0.9, 0.999, nullptr) == DFK_ENOTSUP);
+  }
   EXPECT(dfk_cpb_bias_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 169, 512, 64, nullptr) != 0);
   std::printf("host_check: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);
   return fails ? 1 : 0;

@@ -1,0 +1,128 @@
+"""Device time of the fused AdamW step against the fused SGD step over the C2 model's parameter store
+(build_fused("c2"), bf16 compute: fp32 master + bf16 shadow): dfk_adamw_step_runs against dfk_sgd_step_runs (the
+yardstick, timed in the same process) over the store's own run table with every LayerDrop gate open, and
+FusedAdamW.step (the counter / correction prelude included).  The bytes model is 30 B per element for AdamW
+(p, exp_avg, exp_avg_sq read and written, the gradient read, the shadow written) against SGD's 22 B.
+HIP events on the op's stream around `inner` back-to-back calls, median over `reps` repeats, after a warm-up; the
+cases are timed interleaved in each repeat.  With --step also one C2 step-level pair (graph-replayed TrainStep, B = 8,
+SGD against AdamW), for orientation.  Prints one JSON line.
+Usage: python tools/optim_bench.py [reps] [inner] [--step]"""
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from deepfake_amd import kernels as K  # noqa: E402
+from deepfake_amd.models.fused import CONFIGS, build_fused  # noqa: E402
+from deepfake_amd.optim import FusedAdamW, FusedSGD  # noqa: E402
+from deepfake_amd.params import ParamStore  # noqa: E402
+
+HBM_PEAK = 8e12   # bytes / s
+
+
+def timed(fn, inner):
+    """Milliseconds per call: events recorded on the current stream around `inner` calls."""
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(inner):
+        fn()
+    t1.record()
+    t1.synchronize()
+    return t0.elapsed_time(t1) / inner
+
+
+def interleaved(cases, reps, inner, warm=5):
+    for fn in cases.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(reps):
+        for k, fn in cases.items():
+            ms[k].append(timed(fn, inner))
+    return ms
+
+
+def step_pair(reps, inner):
+    """ms per graph-replayed C2 training step (B = 8, synthetic batch) with each optimizer."""
+    from deepfake_amd import rng
+    from deepfake_amd.ddp import GradBucketer
+    from deepfake_amd.trainer import TrainStep
+    cfg, dev = CONFIGS["c2"], torch.device("cuda")
+    steps = {}
+    for name in ("sgd", "adamw"):
+        torch.manual_seed(1234)
+        rng.manual_seed(1234, 0)
+        model = build_fused(cfg, compute_dtype=torch.bfloat16).to(dev).train()
+        store = ParamStore(model, torch.bfloat16)
+        opt = FusedSGD(store, 1e-4, 0.9, 1e-3) if name == "sgd" else FusedAdamW(store, 1e-4, weight_decay=1e-3)
+        g = torch.Generator(device=dev).manual_seed(1234)
+        feat = (torch.randn(8, cfg["T"], 3, cfg["H"], cfg["W"], device=dev, generator=g),
+                torch.randn(8, 3, 224, 224, device=dev, generator=g),
+                torch.randn(8, int(16000 * cfg["seconds"]), device=dev, generator=g))
+        label = (torch.rand(8, device=dev, generator=g) < 0.5).float()
+        ts = TrainStep(model, store, opt, GradBucketer(store), graph=True)
+        ts(feat, label)
+        if ts.graph is None:
+            raise SystemExit(f"optim_bench: the {name} step was not captured")
+        steps[name] = (lambda ts=ts, feat=feat, label=label: ts(feat, label))
+    ms = interleaved(steps, reps, inner, warm=3)
+    return {k: {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+            for k, v in ms.items()}
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    reps = int(args[0]) if len(args) > 0 else 30
+    inner = int(args[1]) if len(args) > 1 else 20
+    if not torch.cuda.is_available():
+        raise SystemExit("optim_bench: needs the GPU (no CPU timing)")
+    torch.manual_seed(0)
+    model = build_fused("c2", compute_dtype=torch.bfloat16).cuda()
+    store = ParamStore(model, torch.bfloat16)
+    for gate in store.gate:                      # every LayerDrop layer kept: all runs do their work
+        if gate is not None:
+            gate.fill_(1.0)
+    store.grad.normal_(0.0, 1e-3)
+    sgd, adam = FusedSGD(store, 1e-4, 0.9, 1e-3), FusedAdamW(store, 1e-4, weight_decay=1e-3)
+    runs = store.touched_runs(also=adam.cls, every=True)         # the table FusedAdamW.step launches
+    if len(runs) > K.SGD_MAX_RUNS:
+        raise SystemExit(f"optim_bench: {len(runs)} runs, the one-launch kernels take {K.SGD_MAX_RUNS}")
+    n = sum(e - s for s, e, _ in runs)
+    sgd_tab = [(s, e, adam.gates[c], False) for s, e, c in runs]
+    adam_tab = [(s, e, adam.gates[c], c) for s, e, c in runs]
+    b1, b2 = adam.betas
+    K.adamw_prelude(adam.counters, adam.corr, [(c, g) for c, g in enumerate(adam.gates)], b1, b2)
+    cases = {
+        "sgd_step_runs": lambda: K.sgd_step_runs(store.flat, store.grad, sgd.buf, store.shadow, sgd_tab, 0.9, 1e-3,
+                                                 sgd.lr_dev),
+        "adamw_step_runs": lambda: K.adamw_step_runs(store.flat, store.grad, adam.exp_avg, adam.exp_avg_sq,
+                                                     store.shadow, adam_tab, b1, b2, adam.eps, 1e-3, adam.lr_dev,
+                                                     adam.corr),
+        "FusedAdamW.step": adam.step,
+    }
+    ms = interleaved(cases, reps, inner)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    bytes_per = {"sgd_step_runs": 22, "adamw_step_runs": 30, "FusedAdamW.step": 30}
+    out = {"config": "c2", "elements": n, "store_elements": store.numel, "runs": len(runs),
+           "classes": len(adam.gates), "reps": reps, "inner": inner,
+           "ms_median": {k: round(v, 4) for k, v in med.items()},
+           "ms_min": {k: round(min(v), 4) for k, v in ms.items()},
+           "ms_max": {k: round(max(v), 4) for k, v in ms.items()},
+           "TB_per_s": {k: round(bytes_per[k] * n / (med[k] * 1e-3) / 1e12, 3) for k in med},
+           "fraction_of_8TBps": {k: round(bytes_per[k] * n / (med[k] * 1e-3) / HBM_PEAK, 3) for k in med},
+           "adamw_over_sgd": round(med["adamw_step_runs"] / med["sgd_step_runs"], 4), "bytes_ratio": round(30 / 22, 4),
+           "prelude_ms": round(med["FusedAdamW.step"] - med["adamw_step_runs"], 4),
+           "device": torch.cuda.get_device_name(0)}
+    if "--step" in sys.argv:
+        del model, store, sgd, adam, cases
+        torch.cuda.empty_cache()
+        out["c2_step_ms"] = step_pair(max(reps // 3, 3), max(inner // 2, 5))
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
