@@ -17,6 +17,8 @@
   --optimizer {sgd,adamw}  the reference's SGD(momentum 0.9) (default) or the AdamW it keeps beside it
                            (src/trainer.py:78: betas (0.9, 0.999), weight decay --l2_decacy), fused on the device;
                            --adam_beta1, --adam_beta2, --adam_eps set its other hyper-parameters
+  --clip_grad_norm FLOAT   global gradient-norm clipping (torch.nn.utils.clip_grad_norm_ on the mean gradient right
+                           before the step) fused into either optimizer on the device; 0 (default): off
   --video_encoder {swin,inception}   video slot: the north-star Video Swin 3D (default) or the reference's
                            current InceptionVideoClassifier (Inception-ResNet-v2 + NeXtVLAD, train.py:32,44)
 
@@ -92,6 +94,8 @@ def build_parser():
     parser.add_argument('--adam_beta1', type=float, default=0.9)
     parser.add_argument('--adam_beta2', type=float, default=0.999)
     parser.add_argument('--adam_eps', type=float, default=1e-8)
+    parser.add_argument('--clip_grad_norm', type=float, default=0.0,
+                        help='max global gradient norm (clip_grad_norm_ semantics, on the device); 0: no clipping')
     return parser
 
 

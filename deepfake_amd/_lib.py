@@ -132,6 +132,14 @@ SIGNATURES = {
     "dfk_adamw_step": [_VP, _VP, _VP, _VP, _VP, _I64, _VP, _F, C.c_double, C.c_double, _F, _F, _VP, _VP, _F, _VP, _VP],
     "dfk_adamw_step_runs": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _F, C.c_double, C.c_double, _F, _F, _VP, _I32,
                             _F, _VP, _VP],
+    "dfk_grad_sqnorm_runs": [_VP, _VP, _VP, _I32, _F, _VP, _VP],
+    "dfk_grad_clip_coef": [_VP, _I32, _F, _VP, _VP],
+    "dfk_sgd_step_clip": [_VP, _VP, _VP, _VP, _I64, _VP, _F, _F, _F, C.c_int, _VP, _F, _VP, _VP, _VP],
+    "dfk_sgd_step_runs_clip": [_VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _F, _F, _F, _F, _VP, _VP, _VP],
+    "dfk_adamw_step_clip": [_VP, _VP, _VP, _VP, _VP, _I64, _VP, _F, C.c_double, C.c_double, _F, _F, _VP, _VP, _F, _VP,
+                            _VP, _VP],
+    "dfk_adamw_step_runs_clip": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _F, C.c_double, C.c_double, _F, _F, _VP,
+                                 _I32, _F, _VP, _VP, _VP],
     "dfk_im2col2d": [_VP, _I64, _VP, C.POINTER(Conv2dGeo), C.c_int, _VP],
     "dfk_col2im2d": [_VP, _VP, _I64, C.POINTER(Conv2dGeo), C.c_int, C.c_int, _VP],
     "dfk_bn2d_fwd": [_VP, _I64, _VP, _I64, _I64, _I32, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int,

@@ -530,29 +530,61 @@ def wave_normalize(wave, eps=1e-7):
     return out
 
 
+def _opt(t):
+    return L.ptr(t) if t is not None else None
+
+
+def _clip_args(clip_coef, what):
+    """The trailing arguments of an update launch: (..., stream), or (..., clip_coef, stream) for the _clip twin."""
+    if clip_coef is None:
+        return (L.stream(),)
+    if clip_coef.dtype != torch.float32 or clip_coef.numel() != 1:
+        raise ValueError(f"{what}: clip_coef is one device fp32 (grad_clip_coef's out[1:2])")
+    return (L.ptr(clip_coef), L.stream())
+
+
 def sgd_step(param, grad, buf, shadow, lr, momentum, wd, first, lr_dev=None, gate=None, grad_scale=1.0,
-             grad_bf16=None):
-    """grad_scale / grad_bf16: the data-parallel fold (gradient = grad_bf16 or grad, times grad_scale)."""
-    L.check(L.lib().dfk_sgd_step(L.ptr(param), L.ptr(grad), L.ptr(buf), L.ptr(shadow) if shadow is not None else None,
-                                 param.numel(), L.ptr(lr_dev) if lr_dev is not None else None, float(lr),
-                                 float(momentum), float(wd), int(first), L.ptr(gate), float(grad_scale),
-                                 L.ptr(grad_bf16) if grad_bf16 is not None else None, L.stream()), "sgd_step")
+             grad_bf16=None, clip_coef=None):
+    """grad_scale / grad_bf16: the data-parallel fold (gradient = grad_bf16 or grad, times grad_scale).
+    clip_coef (sgd_step_clip): device fp32 coefficient multiplied onto that gradient (dfk_sgd_step_clip)."""
+    fn = L.lib().dfk_sgd_step if clip_coef is None else L.lib().dfk_sgd_step_clip
+    L.check(fn(L.ptr(param), L.ptr(grad), L.ptr(buf), _opt(shadow), param.numel(), _opt(lr_dev), float(lr),
+               float(momentum), float(wd), int(first), L.ptr(gate), float(grad_scale), _opt(grad_bf16),
+               *_clip_args(clip_coef, "sgd_step")), "sgd_step")
+
+
+def sgd_step_clip(param, grad, buf, shadow, lr, momentum, wd, first, clip_coef, **kw):
+    """sgd_step with the gradient times the device clip coefficient (global-norm clipping)."""
+    if clip_coef is None:
+        raise ValueError("sgd_step_clip needs clip_coef")
+    sgd_step(param, grad, buf, shadow, lr, momentum, wd, first, clip_coef=clip_coef, **kw)
 
 
 SGD_MAX_RUNS = 64   # dfk_sgd_step_runs' by-value run table
 
 
-def sgd_step_runs(param, grad, buf, shadow, runs, momentum, wd, lr_dev, grad_scale=1.0, grad_bf16=None):
+def _run_table(runs, what):
+    if not 0 < len(runs) <= SGD_MAX_RUNS:
+        raise ValueError(f"{what} takes 1..{SGD_MAX_RUNS} runs")
+    return (ctypes.c_int64 * (4 * len(runs)))(*[v for s, e, g, x in runs
+                                                for v in (s, e - s, g.data_ptr() if g is not None else 0, int(x))])
+
+
+def sgd_step_runs(param, grad, buf, shadow, runs, momentum, wd, lr_dev, grad_scale=1.0, grad_bf16=None,
+                  clip_coef=None):
     """Every run [(start, end, gate tensor or None, first)] of one SGD step in one launch (same per-element
     arithmetic as sgd_step); the run table is host data copied into the launch arguments."""
-    if not 0 < len(runs) <= SGD_MAX_RUNS:
-        raise ValueError(f"sgd_step_runs takes 1..{SGD_MAX_RUNS} runs")
-    tab = (ctypes.c_int64 * (4 * len(runs)))(*[v for s, e, g, f in runs
-                                          for v in (s, e - s, g.data_ptr() if g is not None else 0, int(bool(f)))])
-    L.check(L.lib().dfk_sgd_step_runs(L.ptr(param), L.ptr(grad), L.ptr(buf), L.ptr(shadow) if shadow is not None
-                                      else None, tab, len(runs), L.ptr(lr_dev), 0.0, float(momentum), float(wd),
-                                      float(grad_scale), L.ptr(grad_bf16) if grad_bf16 is not None else None,
-                                      L.stream()), "sgd_step_runs")
+    tab = _run_table([(s, e, g, bool(f)) for s, e, g, f in runs], "sgd_step_runs")
+    fn = L.lib().dfk_sgd_step_runs if clip_coef is None else L.lib().dfk_sgd_step_runs_clip
+    L.check(fn(L.ptr(param), L.ptr(grad), L.ptr(buf), _opt(shadow), tab, len(runs), L.ptr(lr_dev), 0.0,
+               float(momentum), float(wd), float(grad_scale), _opt(grad_bf16),
+               *_clip_args(clip_coef, "sgd_step_runs")), "sgd_step_runs")
+
+
+def sgd_step_runs_clip(param, grad, buf, shadow, runs, momentum, wd, lr_dev, clip_coef, **kw):
+    if clip_coef is None:
+        raise ValueError("sgd_step_runs_clip needs clip_coef")
+    sgd_step_runs(param, grad, buf, shadow, runs, momentum, wd, lr_dev, clip_coef=clip_coef, **kw)
 
 
 ADAMW_MAX_CLASSES = 64   # dfk_adamw_prelude's by-value class table
@@ -570,29 +602,64 @@ def adamw_prelude(counters, corr, classes, b1, b2):
 
 
 def adamw_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, b1, b2, eps, wd, corr, lr_dev=None, gate=None,
-               grad_scale=1.0, grad_bf16=None):
+               grad_scale=1.0, grad_bf16=None, clip_coef=None):
     """One run of the AdamW step; corr: the run's class's fp32 pair written by adamw_prelude."""
-    L.check(L.lib().dfk_adamw_step(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
-                                   L.ptr(shadow) if shadow is not None else None, param.numel(),
-                                   L.ptr(lr_dev) if lr_dev is not None else None, float(lr), float(b1), float(b2),
-                                   float(eps), float(wd), L.ptr(corr), L.ptr(gate), float(grad_scale),
-                                   L.ptr(grad_bf16) if grad_bf16 is not None else None, L.stream()), "adamw_step")
+    fn = L.lib().dfk_adamw_step if clip_coef is None else L.lib().dfk_adamw_step_clip
+    L.check(fn(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), _opt(shadow), param.numel(),
+               _opt(lr_dev), float(lr), float(b1), float(b2), float(eps), float(wd), L.ptr(corr), L.ptr(gate),
+               float(grad_scale), _opt(grad_bf16), *_clip_args(clip_coef, "adamw_step")), "adamw_step")
+
+
+def adamw_step_clip(param, grad, exp_avg, exp_avg_sq, shadow, lr, b1, b2, eps, wd, corr, clip_coef, **kw):
+    if clip_coef is None:
+        raise ValueError("adamw_step_clip needs clip_coef")
+    adamw_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, b1, b2, eps, wd, corr, clip_coef=clip_coef, **kw)
 
 
 def adamw_step_runs(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, wd, lr_dev, corr, grad_scale=1.0,
-                    grad_bf16=None):
+                    grad_bf16=None, clip_coef=None):
     """Every run [(start, end, gate tensor or None, class index)] of one AdamW step in one launch (same per-element
     arithmetic as adamw_step); corr: the whole fp32 [2 * classes] table written by adamw_prelude."""
-    if not 0 < len(runs) <= SGD_MAX_RUNS:
-        raise ValueError(f"adamw_step_runs takes 1..{SGD_MAX_RUNS} runs")
-    tab = (ctypes.c_int64 * (4 * len(runs)))(*[v for s, e, g, c in runs
-                                          for v in (s, e - s, g.data_ptr() if g is not None else 0, int(c))])
-    L.check(L.lib().dfk_adamw_step_runs(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
-                                        L.ptr(shadow) if shadow is not None else None, tab, len(runs), L.ptr(lr_dev),
-                                        0.0, float(b1), float(b2), float(eps), float(wd), L.ptr(corr),
-                                        corr.numel() // 2, float(grad_scale),
-                                        L.ptr(grad_bf16) if grad_bf16 is not None else None, L.stream()),
-            "adamw_step_runs")
+    tab = _run_table(runs, "adamw_step_runs")
+    fn = L.lib().dfk_adamw_step_runs if clip_coef is None else L.lib().dfk_adamw_step_runs_clip
+    L.check(fn(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), _opt(shadow), tab, len(runs),
+               L.ptr(lr_dev), 0.0, float(b1), float(b2), float(eps), float(wd), L.ptr(corr), corr.numel() // 2,
+               float(grad_scale), _opt(grad_bf16), *_clip_args(clip_coef, "adamw_step_runs")), "adamw_step_runs")
+
+
+def adamw_step_runs_clip(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, wd, lr_dev, corr, clip_coef,
+                         **kw):
+    if clip_coef is None:
+        raise ValueError("adamw_step_runs_clip needs clip_coef")
+    adamw_step_runs(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, wd, lr_dev, corr,
+                    clip_coef=clip_coef, **kw)
+
+
+GNORM_PARTIALS = 2048   # DFK_GNORM_PARTIALS: doubles per slab of dfk_grad_sqnorm_runs
+
+
+def grad_sqnorm_runs(grad, runs, partials, grad_scale=1.0, grad_bf16=None):
+    """Sum of (g * grad_scale)^2 over the runs [(start, end, gate tensor or None)], g read from grad_bf16 when
+    given: chunks of 64 runs, chunk k into partials[k * GNORM_PARTIALS : (k + 1) * GNORM_PARTIALS] (fp64, every
+    entry written).  Returns the number of partials written, grad_clip_coef's n."""
+    chunks = -(-len(runs) // SGD_MAX_RUNS)
+    if not runs or partials.dtype != torch.float64 or partials.numel() < chunks * GNORM_PARTIALS:
+        raise ValueError(f"grad_sqnorm_runs: {len(runs)} runs need {chunks * GNORM_PARTIALS} fp64 partials")
+    for k in range(chunks):
+        part = runs[k * SGD_MAX_RUNS:(k + 1) * SGD_MAX_RUNS]
+        tab = _run_table([(r[0], r[1], r[2], 0) for r in part], "grad_sqnorm_runs")
+        L.check(L.lib().dfk_grad_sqnorm_runs(L.ptr(grad), _opt(grad_bf16), tab, len(part), float(grad_scale),
+                                             L.ptr(partials[k * GNORM_PARTIALS:]), L.stream()), "grad_sqnorm_runs")
+    return chunks * GNORM_PARTIALS
+
+
+def grad_clip_coef(partials, n, max_norm, out):
+    """out (device fp32 [2]) = {norm, coef} = {sqrt(sum of partials[:n]), min(1, max_norm / (norm + 1e-6))}:
+    torch.nn.utils.clip_grad_norm_'s total norm and clip coefficient, computed on the device."""
+    if out.dtype != torch.float32 or out.numel() < 2 or partials.dtype != torch.float64 or partials.numel() < n:
+        raise ValueError("grad_clip_coef: out is fp32 [2], partials fp64 [>= n]")
+    L.check(L.lib().dfk_grad_clip_coef(L.ptr(partials), int(n), float(max_norm), L.ptr(out), L.stream()),
+            "grad_clip_coef")
 
 
 def dropout(x, drop, out=None, group_rows=None):

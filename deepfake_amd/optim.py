@@ -7,6 +7,9 @@ in device memory so a captured graph replays with the scheduler's current lr.
 FusedAdamW: torch.optim.AdamW(betas, eps, weight_decay) in the same form, its
 step counts in device memory too (one per LayerDrop gate class), so a replayed
 graph takes the right bias corrections.
+max_grad_norm (both): torch.nn.utils.clip_grad_norm_(params, max_grad_norm) on the mean gradient right before the
+step, on the device: one reduction pass over the step's runs, a one-workgroup coefficient kernel, and update
+kernels that multiply the gradient by the coefficient they read from device memory.
 """
 import math
 import os
@@ -20,11 +23,39 @@ from . import kernels as K
 _RUNS = os.environ.get("DFK_SGD_RUNS", "1") != "0"
 
 
-class FusedSGD:
+class _GradClip:
+    """Device state of global-norm clipping, allocated once: the fp64 partial slabs (one per chunk of 64 runs the
+    store can produce) and the fp32 pair grad_norm = {norm, coef} of the last step."""
+
+    def _init_clip(self, store, max_grad_norm):
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = self._partials = None
+        if self.max_grad_norm is None:
+            return
+        if not (self.max_grad_norm > 0.0 and math.isfinite(self.max_grad_norm)):
+            raise ValueError(f"{type(self).__name__}: max_grad_norm must be a positive float or None, "
+                             f"got {max_grad_norm}")
+        dev = store.flat.device
+        chunks = max(1, -(-len(store.params) // K.SGD_MAX_RUNS))       # at most one run per parameter
+        self._partials = torch.zeros(chunks * K.GNORM_PARTIALS, device=dev, dtype=torch.float64)
+        self.grad_norm = torch.zeros(2, device=dev, dtype=torch.float32)
+
+    def _clip(self, runs, grad_scale, grad_bf16):
+        """norm and coefficient of this step's runs [(start, end, gate)] -> the device coefficient, or None when
+        clipping is off.  Two launches per 64 runs + one; nothing is allocated and nothing read on the host."""
+        if self.max_grad_norm is None:
+            return None
+        n = K.grad_sqnorm_runs(self.store.grad, runs, self._partials, grad_scale=grad_scale, grad_bf16=grad_bf16)
+        K.grad_clip_coef(self._partials, n, self.max_grad_norm, self.grad_norm)
+        return self.grad_norm[1:2]
+
+
+class FusedSGD(_GradClip):
     folds_grad = True   # step() takes the all-reduced sum and 1 / world itself (TrainStep._fold)
 
-    def __init__(self, store, lr, momentum=0.9, weight_decay=0.0):
+    def __init__(self, store, lr, momentum=0.9, weight_decay=0.0, max_grad_norm=None):
         self.store = store
+        self._init_clip(store, max_grad_norm)
         self.base_lr = float(lr)
         self.momentum, self.weight_decay = float(momentum), float(weight_decay)
         self.buf = torch.zeros_like(store.flat)
@@ -55,16 +86,19 @@ class FusedSGD:
                 if t:
                     self.has_buf[i] = True
         # a LayerDrop-gated run is skipped on the device when its layer was dropped this step
+        ck = {}
+        if self.max_grad_norm is not None and runs:   # the norm of the same runs, gates and fold, then the _clip twins
+            ck["clip_coef"] = self._clip([(s, e, gates.get(k)) for s, e, (f, k) in runs], grad_scale, grad_bf16)
         if _RUNS and 0 < len(runs) <= K.SGD_MAX_RUNS:
             K.sgd_step_runs(st.flat, st.grad, self.buf, st.shadow, [(s, e, gates.get(k), f) for s, e, (f, k) in runs],
                             self.momentum, self.weight_decay, self.lr_dev, grad_scale=grad_scale,
-                            grad_bf16=grad_bf16)
+                            grad_bf16=grad_bf16, **ck)
             self.first = False
             return
         for s, e, (f, k) in runs:
             K.sgd_step(st.flat[s:e], st.grad[s:e], self.buf[s:e], st.shadow[s:e] if st.shadow is not None else None,
                        0.0, self.momentum, self.weight_decay, bool(f), lr_dev=self.lr_dev, gate=gates.get(k),
-                       grad_scale=grad_scale, grad_bf16=grad_bf16[s:e] if grad_bf16 is not None else None)
+                       grad_scale=grad_scale, grad_bf16=grad_bf16[s:e] if grad_bf16 is not None else None, **ck)
         self.first = False
 
     def zero_grad(self):
@@ -74,7 +108,7 @@ class FusedSGD:
         return {"momentum_buffer": self.buf, "lr": self.param_groups[0]["lr"], "first": self.first}
 
 
-class FusedAdamW:
+class FusedAdamW(_GradClip):
     """torch.optim.AdamW(lr, betas, eps, weight_decay; amsgrad / maximize off) with FusedSGD's surface.
 
     Step counts are int32 device memory, one per gate class: class 0 holds the ungated parameters, every distinct
@@ -84,11 +118,12 @@ class FusedAdamW:
     shadow and counter, as torch leaves a grad=None parameter, so a layer dropped in step 1 takes t = 1 in step 2."""
     folds_grad = True
 
-    def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         b1, b2 = float(betas[0]), float(betas[1])
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or not float(eps) > 0.0:
             raise ValueError(f"FusedAdamW: betas must lie in [0, 1) and eps be positive, got {betas}, {eps}")
         self.store = store
+        self._init_clip(store, max_grad_norm)
         self.base_lr = float(lr)
         self.betas, self.eps, self.weight_decay = (b1, b2), float(eps), float(weight_decay)
         dev = store.flat.device
@@ -132,17 +167,22 @@ class FusedAdamW:
         if not runs:
             return
         b1, b2 = self.betas
+        ck = {}
+        if self.max_grad_norm is not None:    # norm and coefficient first, then the prelude and the _clip twins
+            ck["clip_coef"] = self._clip([(s, e, self.gates[c]) for s, e, c in runs], grad_scale, grad_bf16)
         K.adamw_prelude(self.counters, self.corr, [(c, self.gates[c]) for c in sorted({c for _, _, c in runs})], b1, b2)
-        if len(runs) <= K.SGD_MAX_RUNS:
+        # DFK_SGD_RUNS=0 selects the per-run launches only for a clipped step (A/B of the _clip twins): without
+        # clipping FusedAdamW has never read the variable, and its launches stay what they were
+        if (_RUNS or not ck) and len(runs) <= K.SGD_MAX_RUNS:
             K.adamw_step_runs(st.flat, st.grad, self.exp_avg, self.exp_avg_sq, st.shadow,
                               [(s, e, self.gates[c], c) for s, e, c in runs], b1, b2, self.eps, self.weight_decay,
-                              self.lr_dev, self.corr, grad_scale=grad_scale, grad_bf16=grad_bf16)
+                              self.lr_dev, self.corr, grad_scale=grad_scale, grad_bf16=grad_bf16, **ck)
             return
         for s, e, c in runs:
             K.adamw_step(st.flat[s:e], st.grad[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
                          st.shadow[s:e] if st.shadow is not None else None, 0.0, b1, b2, self.eps, self.weight_decay,
                          self.corr[2 * c:2 * c + 2], lr_dev=self.lr_dev, gate=self.gates[c], grad_scale=grad_scale,
-                         grad_bf16=grad_bf16[s:e] if grad_bf16 is not None else None)
+                         grad_bf16=grad_bf16[s:e] if grad_bf16 is not None else None, **ck)
 
     def zero_grad(self):
         self.store.zero_grad()

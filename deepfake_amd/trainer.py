@@ -72,6 +72,24 @@ def check_finite(loss, step, group=None, device="cpu"):
     return loss
 
 
+def clip_arg(args):
+    """--clip_grad_norm as the optimizers' max_grad_norm: None for 0 / absent (off), the positive finite value
+    otherwise; a negative or non-finite value is an error, not a silent "off"."""
+    clip = getattr(args, "clip_grad_norm", None)
+    clip = 0.0 if clip is None else float(clip)
+    if not math.isfinite(clip) or clip < 0:
+        raise ValueError(f"--clip_grad_norm must be a positive finite number (0: off), got {clip}")
+    return clip if clip > 0 else None
+
+
+def check_grad_norm(norm, step):
+    """The device gradient norm of a clipped step at a log step.  It is taken after the all-reduce, from bytes every
+    rank holds alike, so a non-finite norm raises on every rank at this step with no collective of its own."""
+    if not math.isfinite(norm):
+        raise FloatingPointError(f"non-finite gradient norm {norm} at optimizer step {step}")
+    return norm
+
+
 def prepare_video(video, device, augment=False, generator=None, size=224):
     """Frames to the device: fp32 transform output as is; decoded uint8 RGB frames [B,T,H,W,3] transformed on
     the GPU -> [B,T,3,h,w] with the reference's torchvision transforms on PIL images (PIL semantics,
@@ -427,12 +445,16 @@ class Trainer:
         if self.bucketer.enabled:                      # identical replicas: parameters from rank 0
             dist.broadcast(self.store.flat, 0)
             self.store.refresh_shadow()
+        clip = clip_arg(args)
+        self.clip = clip is not None
         if getattr(args, "optimizer", "sgd") == "adamw":   # src/trainer.py:78
             self.optimizer = FusedAdamW(self.store, args.learning_rate,
                                         betas=(getattr(args, "adam_beta1", 0.9), getattr(args, "adam_beta2", 0.999)),
-                                        eps=getattr(args, "adam_eps", 1e-8), weight_decay=args.l2_decacy)
+                                        eps=getattr(args, "adam_eps", 1e-8), weight_decay=args.l2_decacy,
+                                        max_grad_norm=clip)
         else:
-            self.optimizer = FusedSGD(self.store, args.learning_rate, momentum=0.9, weight_decay=args.l2_decacy)
+            self.optimizer = FusedSGD(self.store, args.learning_rate, momentum=0.9, weight_decay=args.l2_decacy,
+                                      max_grad_norm=clip)
         steps_per_epoch = max(1, int(len(self.trainloader) / self.accum_step))
         self.scheduler = CosineAnnealingLR(self.optimizer, T_max=self.train_epochs * steps_per_epoch)
         self.step_fn = TrainStep(model, self.store, self.optimizer, self.bucketer, graph=graph)
@@ -541,11 +563,15 @@ class Trainer:
                         li = loss.item()
                         check_finite(li, t, (self.bucketer.group or dist.group.WORLD) if self.bucketer.enabled
                                      else None, self.store.grad.device)
+                        gn = check_grad_norm(self.optimizer.grad_norm[0].item(), t) if self.clip else None
                         stat.update(li)
                         dt = time.time() - t0
-                        self.logger("| epoch {:2d} | step {:4d} | lr {:.4E} | Train Loss Avg {:3.5f} | clips/s {:.2f}"
-                                    .format(epoch, t, self.optimizer.param_groups[0]["lr"], stat.avg,
-                                            self.log_step * self.accum_step * self.batch_size / max(dt, 1e-9)))
+                        line = "| epoch {:2d} | step {:4d} | lr {:.4E} | Train Loss Avg {:3.5f} | clips/s {:.2f}" \
+                            .format(epoch, t, self.optimizer.param_groups[0]["lr"], stat.avg,
+                                    self.log_step * self.accum_step * self.batch_size / max(dt, 1e-9))
+                        if gn is not None:
+                            line += " | grad norm {:.4E}".format(gn)
+                        self.logger(line)
                         t0 = time.time()
                     if self.model_save and (t + 1) % self.model_save == 0 and last:
                         os.makedirs("checkpoints", exist_ok=True)

@@ -413,6 +413,48 @@ int dfk_adamw_step_runs(float* param, const float* grad, float* exp_avg, float* 
                         float eps, float weight_decay, const float* corr, int32_t nclass, float grad_scale,
                         const void* grad_bf16, hipStream_t stream);
 
+/* Global gradient-norm clipping on the device:
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2, error_if_nonfinite=False) applied to the mean
+ * gradient right before the optimizer step, in three stages that never touch the host (so a captured step replays
+ * with a fresh norm).
+ * 1. dfk_grad_sqnorm_runs: sum of (g * grad_scale)^2 over the runs, g read as the update kernels read it (`grad`, or
+ *    the bf16 bucket copy `grad_bf16` when given; 16-B / 8-B loads per lane, the n % 4 tail one by one).  runs: HOST
+ *    int64 [nruns][4] in dfk_sgd_step_runs' layout (the fourth field is ignored), 1 <= nruns <= 64; more runs go in
+ *    chunks of 64, each chunk writing its own slab.  A run whose gate reads 0 contributes nothing and is not read
+ *    (clip_grad_norm_ skips grad=None parameters).  partials: device double [DFK_GNORM_PARTIALS], one per persistent
+ *    workgroup, EVERY entry written on every call (zero from a workgroup without work).  Each element is converted
+ *    to double and accumulated with an fp64 fma; all sums run in a fixed order: no atomics, bitwise repeatable.
+ * 2. dfk_grad_clip_coef: one workgroup sums the n partials (n = chunks * DFK_GNORM_PARTIALS) in a fixed order in
+ *    double and writes the fp32 pair out[0] = norm = (float)sqrt(sum), out[1] = coef = min(1, max_norm / (norm +
+ *    1e-6f)) in fp32 arithmetic, as clip_grad_norm_ does.  A non-finite norm is not special-cased: Inf gives coef 0,
+ *    NaN gives coef NaN (torch.clamp keeps NaN), and the update propagates them as torch's grad.mul_(coef) would.
+ * 3. The dfk_*_clip twins of the four update entry points: the same arguments plus clip_coef, the device pointer to
+ *    coef (out + 1 above); the gradient of the update is (grad * grad_scale) * coef.  AdamW: two rounded multiplies;
+ *    SGD: fma(grad, round(grad_scale * coef), round(wd * p)), the plain entry point's fma with grad_scale * coef in
+ *    grad_scale's place.  With coef == 1 both give the plain entry point's bits, at every grad_scale.
+ * DFK_EINVAL before any device work: NULL partials / out / clip_coef, max_norm <= 0 or not finite, nruns outside
+ * 1..64, n <= 0 partials, a negative length, and the twins' alignment / run-table rules. */
+#define DFK_GNORM_PARTIALS 2048
+int dfk_grad_sqnorm_runs(const float* grad, const void* grad_bf16, const int64_t* runs, int32_t nruns,
+                         float grad_scale, double* partials, hipStream_t stream);
+int dfk_grad_clip_coef(const double* partials, int32_t n, float max_norm, float* out, hipStream_t stream);
+int dfk_sgd_step_clip(float* param, const float* grad, float* momentum_buf, void* bf16_shadow, int64_t n,
+                      const float* lr_dev, float lr, float momentum, float weight_decay, int first_step,
+                      const float* gate, float grad_scale, const void* grad_bf16, const float* clip_coef,
+                      hipStream_t stream);
+int dfk_sgd_step_runs_clip(float* param, const float* grad, float* momentum_buf, void* bf16_shadow,
+                           const int64_t* runs, int32_t nruns, const float* lr_dev, float lr, float momentum,
+                           float weight_decay, float grad_scale, const void* grad_bf16, const float* clip_coef,
+                           hipStream_t stream);
+int dfk_adamw_step_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                        int64_t n, const float* lr_dev, float lr, double b1, double b2, float eps, float weight_decay,
+                        const float* corr, const float* gate, float grad_scale, const void* grad_bf16,
+                        const float* clip_coef, hipStream_t stream);
+int dfk_adamw_step_runs_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                             const int64_t* runs, int32_t nruns, const float* lr_dev, float lr, double b1, double b2,
+                             float eps, float weight_decay, const float* corr, int32_t nclass, float grad_scale,
+                             const void* grad_bf16, const float* clip_coef, hipStream_t stream);
+
 /* y = x * mask / (1 - p) over [rows, cols] (row stride ld; y may alias x): nn.Dropout / DropPath as a
  * standalone pass, and the backward of every fused dropout site (the same mask applied to the gradient). */
 int dfk_dropout(const void* x, void* y, int64_t rows, int32_t cols, int64_t ld, const dfk_drop* drop, int dtype,

@@ -1,7 +1,8 @@
 // Host-side checks of libdfk under AddressSanitizer (CPU only; no kernel is launched).  Exercises the C ABI's
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
 // conv0, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
-// dims, the AdamW entry points' buffers / run table / hyper-parameters), which must return DFK_EINVAL before touching
+// dims, the AdamW entry points' buffers / run table / hyper-parameters, the gradient-clipping entry points' slab /
+// coefficient / max_norm / run table), which must return DFK_EINVAL before touching
 // the device.  Built and run by tools/asan/run.sh.
 #include <cstdio>
 #include <cstring>
@@ -229,6 +230,72 @@ int main() {
     EXPECT(dfk_adamw_prelude(cnt, fx, 1, cls + 2, 1, 0.9, 0.999, nullptr) == DFK_EINVAL);   // class 1 of 1
     EXPECT(dfk_adamw_prelude(cnt, fx, 3, cls + 2, 2, 0.9, 0.999, nullptr) == DFK_EINVAL);   // class 1 listed twice
     EXPECT(dfk_adamw_prelude(cnt, fx, 65, cls, 2, 0.9, 0.999, nullptr) == DFK_ENOTSUP);
+  }
+  {
+    // gradient-norm clipping: the norm / coefficient entry points and the _clip twins reject malformed calls
+    float* fx = reinterpret_cast<float*>(0x10000);
+    float* odd = reinterpret_cast<float*>(0x10004);
+    double* part = reinterpret_cast<double*>(0x30000);
+    int64_t runs[65 * 4];
+    for (int r = 0; r < 65; ++r) { runs[4 * r] = 64 * r; runs[4 * r + 1] = 40; runs[4 * r + 2] = 0; runs[4 * r + 3] = 0; }
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, runs, 2, 1.f, nullptr, nullptr) == DFK_EINVAL);      // no slab
+    EXPECT(dfk_grad_sqnorm_runs(nullptr, nullptr, runs, 2, 1.f, part, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, nullptr, 2, 1.f, part, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, runs, 0, 1.f, part, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, runs, -1, 1.f, part, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, runs, 65, 1.f, part, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_sqnorm_runs(odd, nullptr, runs, 2, 1.f, part, nullptr) == DFK_EINVAL);        // misaligned grad
+    EXPECT(dfk_grad_sqnorm_runs(fx, odd, runs, 2, 1.f, part, nullptr) == DFK_EINVAL);             // grad_bf16 not 8-B
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, runs, 2, 1.f, reinterpret_cast<double*>(odd), nullptr) == DFK_EINVAL);
+    runs[4] = 66;                                                          // run start not a multiple of 4
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, runs, 2, 1.f, part, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_clip(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, fx, nullptr) ==
+           DFK_EINVAL);
+    runs[4] = 64; runs[5] = -8;                                            // negative n
+    EXPECT(dfk_grad_sqnorm_runs(fx, nullptr, runs, 2, 1.f, part, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_clip(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
+                                    nullptr, fx, nullptr) == DFK_EINVAL);
+    runs[5] = 40;
+    const float inf = 1.f / 0.f, nan = inf - inf;
+    EXPECT(dfk_grad_clip_coef(nullptr, 2048, 1.f, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_clip_coef(part, 2048, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_clip_coef(part, 0, 1.f, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_clip_coef(part, -2048, 1.f, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_clip_coef(part, 2048, 0.f, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_clip_coef(part, 2048, -1.f, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_clip_coef(part, 2048, inf, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_grad_clip_coef(part, 2048, nan, fx, nullptr) == DFK_EINVAL);
+    // the twins: no coefficient, then their twins' own rules
+    EXPECT(dfk_sgd_step_clip(fx, fx, fx, nullptr, 16, fx, 0.f, 0.9f, 0.f, 0, nullptr, 1.f, nullptr, nullptr, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_sgd_step_clip(fx, fx, fx, nullptr, -4, fx, 0.f, 0.9f, 0.f, 0, nullptr, 1.f, nullptr, fx, nullptr) ==
+           DFK_EINVAL);                                                    // negative length
+    EXPECT(dfk_sgd_step_clip(odd, fx, fx, nullptr, 16, fx, 0.f, 0.9f, 0.f, 0, nullptr, 1.f, nullptr, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_sgd_step_clip(fx, fx, fx, nullptr, 16, fx, 0.f, 0.9f, 0.f, 0, nullptr, 1.f, odd, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_clip(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_clip(fx, fx, fx, nullptr, runs, 0, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_clip(fx, fx, fx, nullptr, runs, 65, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_clip(fx, fx, odd, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_adamw_step_clip(fx, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                               nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_clip(fx, fx, fx, fx, nullptr, -4, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                               fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_clip(fx, fx, fx, odd, nullptr, 16, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, nullptr, 1.f, nullptr,
+                               fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_clip(fx, fx, fx, fx, nullptr, 16, fx, 0.f, 0.9, 0.999, 0.f, 0.f, fx, nullptr, 1.f, nullptr,
+                               fx, nullptr) == DFK_EINVAL);                // eps = 0
+    EXPECT(dfk_adamw_step_runs_clip(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
+                                    nullptr, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_clip(fx, fx, fx, fx, nullptr, runs, 65, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
+                                    nullptr, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_clip(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
+                                    odd, fx, nullptr) == DFK_EINVAL);      // grad_bf16 not 8-B aligned
   }
   EXPECT(dfk_cpb_bias_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 169, 512, 64, nullptr) != 0);
   std::printf("host_check: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);

@@ -4,8 +4,10 @@ yardstick, timed in the same process) over the store's own run table with every 
 FusedAdamW.step (the counter / correction prelude included).  The bytes model is 30 B per element for AdamW
 (p, exp_avg, exp_avg_sq read and written, the gradient read, the shadow written) against SGD's 22 B.
 HIP events on the op's stream around `inner` back-to-back calls, median over `reps` repeats, after a warm-up; the
-cases are timed interleaved in each repeat.  With --step also one C2 step-level pair (graph-replayed TrainStep, B = 8,
-SGD against AdamW), for orientation.  Prints one JSON line.
+cases are timed interleaved in each repeat.  Gradient clipping: the norm pass (dfk_grad_sqnorm_runs +
+dfk_grad_clip_coef, 4 B per element, so 4/22 of the yardstick by the bytes model) alone, and FusedSGD.step /
+FusedAdamW.step with max_grad_norm on and off.  With --step also the C2 step level (graph-replayed TrainStep, B = 8,
+SGD and AdamW, each with clipping off and on), for orientation.  Prints one JSON line.
 Usage: python tools/optim_bench.py [reps] [inner] [--step]"""
 import json
 import os
@@ -53,12 +55,14 @@ def step_pair(reps, inner):
     from deepfake_amd.trainer import TrainStep
     cfg, dev = CONFIGS["c2"], torch.device("cuda")
     steps = {}
-    for name in ("sgd", "adamw"):
+    for name in ("sgd", "sgd+clip", "adamw", "adamw+clip"):
+        clip = 1.0 if name.endswith("+clip") else None
         torch.manual_seed(1234)
         rng.manual_seed(1234, 0)
         model = build_fused(cfg, compute_dtype=torch.bfloat16).to(dev).train()
         store = ParamStore(model, torch.bfloat16)
-        opt = FusedSGD(store, 1e-4, 0.9, 1e-3) if name == "sgd" else FusedAdamW(store, 1e-4, weight_decay=1e-3)
+        opt = FusedSGD(store, 1e-4, 0.9, 1e-3, max_grad_norm=clip) if name.startswith("sgd") else \
+            FusedAdamW(store, 1e-4, weight_decay=1e-3, max_grad_norm=clip)
         g = torch.Generator(device=dev).manual_seed(1234)
         feat = (torch.randn(8, cfg["T"], 3, cfg["H"], cfg["W"], device=dev, generator=g),
                 torch.randn(8, 3, 224, 224, device=dev, generator=g),
@@ -88,6 +92,8 @@ def main():
             gate.fill_(1.0)
     store.grad.normal_(0.0, 1e-3)
     sgd, adam = FusedSGD(store, 1e-4, 0.9, 1e-3), FusedAdamW(store, 1e-4, weight_decay=1e-3)
+    sgd_c = FusedSGD(store, 1e-4, 0.9, 1e-3, max_grad_norm=1.0)
+    adam_c = FusedAdamW(store, 1e-4, weight_decay=1e-3, max_grad_norm=1.0)
     runs = store.touched_runs(also=adam.cls, every=True)         # the table FusedAdamW.step launches
     if len(runs) > K.SGD_MAX_RUNS:
         raise SystemExit(f"optim_bench: {len(runs)} runs, the one-launch kernels take {K.SGD_MAX_RUNS}")
@@ -95,6 +101,12 @@ def main():
     sgd_tab = [(s, e, adam.gates[c], False) for s, e, c in runs]
     adam_tab = [(s, e, adam.gates[c], c) for s, e, c in runs]
     b1, b2 = adam.betas
+    norm_tab = [(s, e, adam.gates[c]) for s, e, c in runs]
+    part = torch.zeros(K.GNORM_PARTIALS, device="cuda", dtype=torch.float64)
+    pair = torch.zeros(2, device="cuda")
+
+    def grad_norm():
+        K.grad_clip_coef(part, K.grad_sqnorm_runs(store.grad, norm_tab, part), 1.0, pair)
     K.adamw_prelude(adam.counters, adam.corr, [(c, g) for c, g in enumerate(adam.gates)], b1, b2)
     cases = {
         "sgd_step_runs": lambda: K.sgd_step_runs(store.flat, store.grad, sgd.buf, store.shadow, sgd_tab, 0.9, 1e-3,
@@ -103,10 +115,15 @@ def main():
                                                      store.shadow, adam_tab, b1, b2, adam.eps, 1e-3, adam.lr_dev,
                                                      adam.corr),
         "FusedAdamW.step": adam.step,
+        "grad_norm": grad_norm,
+        "FusedSGD.step": sgd.step,
+        "FusedSGD.step+clip": sgd_c.step,
+        "FusedAdamW.step+clip": adam_c.step,
     }
     ms = interleaved(cases, reps, inner)
     med = {k: statistics.median(v) for k, v in ms.items()}
-    bytes_per = {"sgd_step_runs": 22, "adamw_step_runs": 30, "FusedAdamW.step": 30}
+    bytes_per = {"sgd_step_runs": 22, "adamw_step_runs": 30, "FusedAdamW.step": 30, "grad_norm": 4,
+                 "FusedSGD.step": 22, "FusedSGD.step+clip": 26, "FusedAdamW.step+clip": 34}
     out = {"config": "c2", "elements": n, "store_elements": store.numel, "runs": len(runs),
            "classes": len(adam.gates), "reps": reps, "inner": inner,
            "ms_median": {k: round(v, 4) for k, v in med.items()},
@@ -116,9 +133,14 @@ def main():
            "fraction_of_8TBps": {k: round(bytes_per[k] * n / (med[k] * 1e-3) / HBM_PEAK, 3) for k in med},
            "adamw_over_sgd": round(med["adamw_step_runs"] / med["sgd_step_runs"], 4), "bytes_ratio": round(30 / 22, 4),
            "prelude_ms": round(med["FusedAdamW.step"] - med["adamw_step_runs"], 4),
+           "grad_norm_over_sgd": round(med["grad_norm"] / med["sgd_step_runs"], 4), "grad_norm_bytes_ratio": round(4 / 22, 4),
+           "grad_norm_over_bytes_model": round(med["grad_norm"] / (med["sgd_step_runs"] * 4 / 22), 3),
+           "clip_cost_ms": {"sgd": round(med["FusedSGD.step+clip"] - med["FusedSGD.step"], 4),
+                            "adamw": round(med["FusedAdamW.step+clip"] - med["FusedAdamW.step"], 4)},
+           "grad_norm_value": [round(v, 6) for v in adam_c.grad_norm.tolist()],
            "device": torch.cuda.get_device_name(0)}
     if "--step" in sys.argv:
-        del model, store, sgd, adam, cases
+        del model, store, sgd, adam, sgd_c, adam_c, cases
         torch.cuda.empty_cache()
         out["c2_step_ms"] = step_pair(max(reps // 3, 3), max(inner // 2, 5))
     print(json.dumps(out), flush=True)
