@@ -134,12 +134,6 @@ SIGNATURES = {
                             _F, _VP, _VP],
     "dfk_grad_sqnorm_runs": [_VP, _VP, _VP, _I32, _F, _VP, _VP],
     "dfk_grad_clip_coef": [_VP, _I32, _F, _VP, _VP],
-    "dfk_sgd_step_clip": [_VP, _VP, _VP, _VP, _I64, _VP, _F, _F, _F, C.c_int, _VP, _F, _VP, _VP, _VP],
-    "dfk_sgd_step_runs_clip": [_VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _F, _F, _F, _F, _VP, _VP, _VP],
-    "dfk_adamw_step_clip": [_VP, _VP, _VP, _VP, _VP, _I64, _VP, _F, C.c_double, C.c_double, _F, _F, _VP, _VP, _F, _VP,
-                            _VP, _VP],
-    "dfk_adamw_step_runs_clip": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _F, C.c_double, C.c_double, _F, _F, _VP,
-                                 _I32, _F, _VP, _VP, _VP],
     "dfk_im2col2d": [_VP, _I64, _VP, C.POINTER(Conv2dGeo), C.c_int, _VP],
     "dfk_col2im2d": [_VP, _VP, _I64, C.POINTER(Conv2dGeo), C.c_int, C.c_int, _VP],
     "dfk_bn2d_fwd": [_VP, _I64, _VP, _I64, _I64, _I32, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int,
@@ -172,6 +166,10 @@ SIGNATURES = {
     "dfk_patch_embed_fwd": [C.POINTER(PatchEmbedArgs), _VP],
     "dfk_patch_embed_bwd": [C.POINTER(PatchEmbedArgs), _VP, _VP],
 }
+
+# the _clip twins: their twin's arguments with the clip-coefficient pointer in front of the stream
+for _n in ("dfk_sgd_step", "dfk_sgd_step_runs", "dfk_adamw_step", "dfk_adamw_step_runs"):
+    SIGNATURES[_n + "_clip"] = SIGNATURES[_n][:-1] + [_VP, SIGNATURES[_n][-1]]
 
 _lib = None
 RESTYPES = {"dfk_mel_workspace": _I64, "dfk_mel_resampled_workspace": _I64, "dfk_w2v_conv0_bwd_workspace": _I64, "dfk_w2v_conv0_fwd_workspace": _I64, "dfk_layernorm_bwd_workspace": _I64, "dfk_wattn_bwd_workspace": _I64, "dfk_wattn_table_workspace": _I64, "dfk_gemm_workspace": _I64}

@@ -534,6 +534,12 @@ def _opt(t):
     return L.ptr(t) if t is not None else None
 
 
+# Limits of the by-value tables in the launch arguments (csrc/optim.hip) and the norm pass's slab
+SGD_MAX_RUNS = 64        # runs per dfk_*_step_runs / dfk_grad_sqnorm_runs call (kMaxRuns)
+ADAMW_MAX_CLASSES = 64   # gate classes of dfk_adamw_prelude (kAdamwMaxClasses)
+GNORM_PARTIALS = 2048    # DFK_GNORM_PARTIALS: doubles per slab of dfk_grad_sqnorm_runs
+
+
 def _clip_args(clip_coef, what):
     """The trailing arguments of an update launch: (..., stream), or (..., clip_coef, stream) for the _clip twin."""
     if clip_coef is None:
@@ -553,14 +559,21 @@ def sgd_step(param, grad, buf, shadow, lr, momentum, wd, first, lr_dev=None, gat
                *_clip_args(clip_coef, "sgd_step")), "sgd_step")
 
 
-def sgd_step_clip(param, grad, buf, shadow, lr, momentum, wd, first, clip_coef, **kw):
-    """sgd_step with the gradient times the device clip coefficient (global-norm clipping)."""
-    if clip_coef is None:
-        raise ValueError("sgd_step_clip needs clip_coef")
-    sgd_step(param, grad, buf, shadow, lr, momentum, wd, first, clip_coef=clip_coef, **kw)
+def _clip_twin(fn):
+    """fn_clip(*fn's positional arguments, clip_coef, **kw): fn with the gradient times the device clip coefficient
+    (global-norm clipping), which the twin requires."""
+    def twin(*args, **kw):
+        if "clip_coef" not in kw:
+            *args, kw["clip_coef"] = args
+        if kw["clip_coef"] is None:
+            raise ValueError(f"{name}_clip needs clip_coef")
+        globals()[name](*args, **kw)       # looked up per call, as a def would: tests swap in stand-ins
+    name = fn.__name__
+    twin.__name__ = twin.__qualname__ = f"{name}_clip"
+    return twin
 
 
-SGD_MAX_RUNS = 64   # dfk_sgd_step_runs' by-value run table
+sgd_step_clip = _clip_twin(sgd_step)
 
 
 def _run_table(runs, what):
@@ -581,13 +594,7 @@ def sgd_step_runs(param, grad, buf, shadow, runs, momentum, wd, lr_dev, grad_sca
                *_clip_args(clip_coef, "sgd_step_runs")), "sgd_step_runs")
 
 
-def sgd_step_runs_clip(param, grad, buf, shadow, runs, momentum, wd, lr_dev, clip_coef, **kw):
-    if clip_coef is None:
-        raise ValueError("sgd_step_runs_clip needs clip_coef")
-    sgd_step_runs(param, grad, buf, shadow, runs, momentum, wd, lr_dev, clip_coef=clip_coef, **kw)
-
-
-ADAMW_MAX_CLASSES = 64   # dfk_adamw_prelude's by-value class table
+sgd_step_runs_clip = _clip_twin(sgd_step_runs)
 
 
 def adamw_prelude(counters, corr, classes, b1, b2):
@@ -610,10 +617,7 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, b1, b2, eps, wd, co
                float(grad_scale), _opt(grad_bf16), *_clip_args(clip_coef, "adamw_step")), "adamw_step")
 
 
-def adamw_step_clip(param, grad, exp_avg, exp_avg_sq, shadow, lr, b1, b2, eps, wd, corr, clip_coef, **kw):
-    if clip_coef is None:
-        raise ValueError("adamw_step_clip needs clip_coef")
-    adamw_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, b1, b2, eps, wd, corr, clip_coef=clip_coef, **kw)
+adamw_step_clip = _clip_twin(adamw_step)
 
 
 def adamw_step_runs(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, wd, lr_dev, corr, grad_scale=1.0,
@@ -627,15 +631,7 @@ def adamw_step_runs(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps,
                float(grad_scale), _opt(grad_bf16), *_clip_args(clip_coef, "adamw_step_runs")), "adamw_step_runs")
 
 
-def adamw_step_runs_clip(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, wd, lr_dev, corr, clip_coef,
-                         **kw):
-    if clip_coef is None:
-        raise ValueError("adamw_step_runs_clip needs clip_coef")
-    adamw_step_runs(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, wd, lr_dev, corr,
-                    clip_coef=clip_coef, **kw)
-
-
-GNORM_PARTIALS = 2048   # DFK_GNORM_PARTIALS: doubles per slab of dfk_grad_sqnorm_runs
+adamw_step_runs_clip = _clip_twin(adamw_step_runs)
 
 
 def grad_sqnorm_runs(grad, runs, partials, grad_scale=1.0, grad_bf16=None):

@@ -23,11 +23,19 @@ from . import kernels as K
 _RUNS = os.environ.get("DFK_SGD_RUNS", "1") != "0"
 
 
-class _GradClip:
-    """Device state of global-norm clipping, allocated once: the fp64 partial slabs (one per chunk of 64 runs the
-    store can produce) and the fp32 pair grad_norm = {norm, coef} of the last step."""
+class _Fused:
+    """What FusedSGD and FusedAdamW share: the store, the learning rate in device memory (a captured graph replays
+    with the scheduler's current lr), and the device state of global-norm clipping, allocated once: the fp64 partial
+    slabs (one per chunk of 64 runs the store can produce) and the fp32 pair grad_norm = {norm, coef} of the last
+    step."""
+    folds_grad = True   # step() takes the all-reduced sum and 1 / world itself (TrainStep._fold)
 
-    def _init_clip(self, store, max_grad_norm):
+    def __init__(self, store, lr, max_grad_norm):
+        self.store = store
+        self.base_lr = float(lr)
+        dev = store.flat.device
+        self.lr_dev = torch.full((1,), self.base_lr, device=dev, dtype=torch.float32)
+        self.param_groups = [{"lr": self.base_lr, "initial_lr": self.base_lr}]
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.grad_norm = self._partials = None
         if self.max_grad_norm is None:
@@ -35,10 +43,16 @@ class _GradClip:
         if not (self.max_grad_norm > 0.0 and math.isfinite(self.max_grad_norm)):
             raise ValueError(f"{type(self).__name__}: max_grad_norm must be a positive float or None, "
                              f"got {max_grad_norm}")
-        dev = store.flat.device
         chunks = max(1, -(-len(store.params) // K.SGD_MAX_RUNS))       # at most one run per parameter
         self._partials = torch.zeros(chunks * K.GNORM_PARTIALS, device=dev, dtype=torch.float64)
         self.grad_norm = torch.zeros(2, device=dev, dtype=torch.float32)
+
+    def set_lr(self, lr):
+        self.param_groups[0]["lr"] = float(lr)
+        self.lr_dev.fill_(float(lr))
+
+    def zero_grad(self):
+        self.store.zero_grad()
 
     def _clip(self, runs, grad_scale, grad_bf16):
         """norm and coefficient of this step's runs [(start, end, gate)] -> the device coefficient, or None when
@@ -49,24 +63,19 @@ class _GradClip:
         K.grad_clip_coef(self._partials, n, self.max_grad_norm, self.grad_norm)
         return self.grad_norm[1:2]
 
+    @staticmethod
+    def _cut(x, s, e):
+        """x[s:e] of an optional flat buffer (the shadow, the bf16 bucket gradient)"""
+        return x[s:e] if x is not None else None
 
-class FusedSGD(_GradClip):
-    folds_grad = True   # step() takes the all-reduced sum and 1 / world itself (TrainStep._fold)
 
+class FusedSGD(_Fused):
     def __init__(self, store, lr, momentum=0.9, weight_decay=0.0, max_grad_norm=None):
-        self.store = store
-        self._init_clip(store, max_grad_norm)
-        self.base_lr = float(lr)
+        super().__init__(store, lr, max_grad_norm)
         self.momentum, self.weight_decay = float(momentum), float(weight_decay)
         self.buf = torch.zeros_like(store.flat)
-        self.lr_dev = torch.full((1,), self.base_lr, device=store.flat.device, dtype=torch.float32)
-        self.param_groups = [{"lr": self.base_lr, "initial_lr": self.base_lr}]
         self.first = True
         self.has_buf = [False] * len(store.params)   # torch: momentum buffer created at a param's first grad
-
-    def set_lr(self, lr):
-        self.param_groups[0]["lr"] = float(lr)
-        self.lr_dev.fill_(float(lr))
 
     def step(self, first=None, grad_scale=1.0, grad_bf16=None):
         """One SGD step over the parameters that received a gradient (torch skips grad=None:
@@ -96,19 +105,16 @@ class FusedSGD(_GradClip):
             self.first = False
             return
         for s, e, (f, k) in runs:
-            K.sgd_step(st.flat[s:e], st.grad[s:e], self.buf[s:e], st.shadow[s:e] if st.shadow is not None else None,
-                       0.0, self.momentum, self.weight_decay, bool(f), lr_dev=self.lr_dev, gate=gates.get(k),
-                       grad_scale=grad_scale, grad_bf16=grad_bf16[s:e] if grad_bf16 is not None else None, **ck)
+            K.sgd_step(st.flat[s:e], st.grad[s:e], self.buf[s:e], self._cut(st.shadow, s, e), 0.0, self.momentum,
+                       self.weight_decay, bool(f), lr_dev=self.lr_dev, gate=gates.get(k), grad_scale=grad_scale,
+                       grad_bf16=self._cut(grad_bf16, s, e), **ck)
         self.first = False
-
-    def zero_grad(self):
-        self.store.zero_grad()
 
     def state_dict(self):
         return {"momentum_buffer": self.buf, "lr": self.param_groups[0]["lr"], "first": self.first}
 
 
-class FusedAdamW(_GradClip):
+class FusedAdamW(_Fused):
     """torch.optim.AdamW(lr, betas, eps, weight_decay; amsgrad / maximize off) with FusedSGD's surface.
 
     Step counts are int32 device memory, one per gate class: class 0 holds the ungated parameters, every distinct
@@ -116,21 +122,16 @@ class FusedAdamW(_GradClip):
     counter of every class whose gate is open and writes its bias corrections, then the update over the runs
     (dfk_adamw_step_runs; one dfk_adamw_step per run beyond 64 runs).  A gated-off class keeps parameters, moments,
     shadow and counter, as torch leaves a grad=None parameter, so a layer dropped in step 1 takes t = 1 in step 2."""
-    folds_grad = True
 
     def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         b1, b2 = float(betas[0]), float(betas[1])
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or not float(eps) > 0.0:
             raise ValueError(f"FusedAdamW: betas must lie in [0, 1) and eps be positive, got {betas}, {eps}")
-        self.store = store
-        self._init_clip(store, max_grad_norm)
-        self.base_lr = float(lr)
+        super().__init__(store, lr, max_grad_norm)
         self.betas, self.eps, self.weight_decay = (b1, b2), float(eps), float(weight_decay)
         dev = store.flat.device
         self.exp_avg = torch.zeros_like(store.flat)
         self.exp_avg_sq = torch.zeros_like(store.flat)
-        self.lr_dev = torch.full((1,), self.base_lr, device=dev, dtype=torch.float32)
-        self.param_groups = [{"lr": self.base_lr, "initial_lr": self.base_lr}]
         self.gates, self.cls, seen = [None], [], {}
         for g in store.gate:
             if g is not None and id(g) not in seen:
@@ -142,10 +143,6 @@ class FusedAdamW(_GradClip):
         self.counters = torch.zeros(len(self.gates), device=dev, dtype=torch.int32)
         self.corr = torch.zeros(2 * len(self.gates), device=dev, dtype=torch.float32)
         self.active = None   # per parameter: stepped by the eager steps so far (fixed at the first step)
-
-    def set_lr(self, lr):
-        self.param_groups[0]["lr"] = float(lr)
-        self.lr_dev.fill_(float(lr))
 
     def step(self, first=None, grad_scale=1.0, grad_bf16=None):
         """One AdamW step over the parameters that received a gradient (all of them without bookkeeping, e.g. under
@@ -180,12 +177,9 @@ class FusedAdamW(_GradClip):
             return
         for s, e, c in runs:
             K.adamw_step(st.flat[s:e], st.grad[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
-                         st.shadow[s:e] if st.shadow is not None else None, 0.0, b1, b2, self.eps, self.weight_decay,
+                         self._cut(st.shadow, s, e), 0.0, b1, b2, self.eps, self.weight_decay,
                          self.corr[2 * c:2 * c + 2], lr_dev=self.lr_dev, gate=self.gates[c], grad_scale=grad_scale,
-                         grad_bf16=grad_bf16[s:e] if grad_bf16 is not None else None, **ck)
-
-    def zero_grad(self):
-        self.store.zero_grad()
+                         grad_bf16=self._cut(grad_bf16, s, e), **ck)
 
     def state_dict(self):
         """The live state (as torch's): moments over the flat store, the per-class device step counts, lr and the

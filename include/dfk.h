@@ -367,7 +367,10 @@ int dfk_posconv_wnorm_bwd(const float* v, const float* g, const float* norm, con
 /* torch.optim.SGD(momentum, weight_decay) step over a flat fp32 parameter
  * buffer (src/trainer.py:80-84,295), optionally writing the bf16 compute
  * shadow of the updated parameters in the same pass; lr read from device
- * memory when lr_dev != NULL (graph-replay safe CosineAnnealingLR). */
+ * memory when lr_dev != NULL (graph-replay safe CosineAnnealingLR).
+ * param / grad / momentum_buf 16-B aligned, grad_bf16 / bf16_shadow (when given) 8-B aligned, DFK_EINVAL otherwise:
+ * the shadow is written in 8-B quads like every other update entry point's, so a run starts at a multiple of 4
+ * elements of the store. */
 int dfk_sgd_step(float* param, const float* grad, float* momentum_buf, void* bf16_shadow, int64_t n,
                  const float* lr_dev, float lr, float momentum, float weight_decay, int first_step,
                  const float* gate, float grad_scale, const void* grad_bf16, hipStream_t stream);

@@ -151,19 +151,39 @@ def test_gate_and_counters():
         assert torch.equal(f.p[s:e].cpu(), p0[s:e]) and not f.m[s:e].any() and not f.v[s:e].any()
 
 
-@pytest.mark.parametrize("bf16_grad", [False, True])
-@pytest.mark.parametrize("grad_scale", [1.0, 0.25])
-def test_runs_one_launch_matches_per_run(grad_scale, bf16_grad):
+def _ragged_five(on, off):
+    """(n, runs, classes, counters after two steps, untouched ranges, a range that must change, a shadow range)"""
+    runs = [(0, 4, None, 0), (4, 9, on, 1), (12, 2059, off, 2), (2060, 4109, on, 1), (4112, 8211, None, 0)]
+    untouched = ((9, 12), (12, 2059), (2059, 2060), (4109, 4112), (8211, 8216))
+    return 8216, runs, [(0, None), (1, on), (2, off)], [2, 2, 0], untouched, (2060, 4109), (4112, 8211)
+
+
+def _full_table(on, off):
+    """Exactly 64 runs in 64 classes, the limit of both tables (the last slot, prefix[64], class 63): 63 runs of
+    lengths cycling 1..9 at starts 12 r, then one of 2049 elements (two workgroups and a tail) in class 63 behind an
+    open gate; class 33 is gated off."""
+    gate = {33: off, 63: on}
+    runs = [(12 * r, 12 * r + 1 + r % 9, gate.get(r), r) for r in range(63)] + [(756, 756 + 2049, on, 63)]
+    untouched = tuple((runs[r][1], runs[r + 1][0]) for r in range(63)) + ((runs[33][0], runs[33][1]), (2805, 2808))
+    counters = [0 if c == 33 else 2 for c in range(64)]
+    return 2808, runs, [(c, gate.get(c)) for c in range(64)], counters, untouched, (756, 2805), (756, 2805)
+
+
+@pytest.mark.parametrize("grad_scale,bf16_grad,table",
+                         [(1.0, False, _ragged_five), (0.25, False, _ragged_five), (1.0, True, _ragged_five),
+                          (0.25, True, _ragged_five), (1.0, False, _full_table), (0.25, True, _full_table)],
+                         ids=["1.0-False", "0.25-False", "1.0-True", "0.25-True", "64runs-1.0-False",
+                              "64runs-0.25-True"])
+def test_runs_one_launch_matches_per_run(grad_scale, bf16_grad, table):
     """dfk_adamw_step_runs over 5 runs (lengths 4, 5, 2047, 2049, 4099, starts multiples of 4) against one
     dfk_adamw_step per run, bit for bit over two steps: an ungated class and two gated ones, one of them off; the
-    data-parallel fold (grad_scale, bf16 bucket gradient — the fp32 gradient is then NaN and must not be read)."""
-    n = 8216
+    data-parallel fold (grad_scale, bf16 bucket gradient — the fp32 gradient is then NaN and must not be read).
+    Also over a full table of 64 runs in 64 classes."""
+    on, off = torch.ones(1, device=DEV), torch.zeros(1, device=DEV)
+    n, runs, classes, counters, untouched, changed, shadowed = table(on, off)
     gen = torch.Generator().manual_seed(5)
     p0 = torch.randn(n, generator=gen)
-    on, off = torch.ones(1, device=DEV), torch.zeros(1, device=DEV)
-    runs = [(0, 4, None, 0), (4, 9, on, 1), (12, 2059, off, 2), (2060, 4109, on, 1), (4112, 8211, None, 0)]
-    classes = [(0, None), (1, on), (2, off)]
-    a, b = Flat(p0, 3), Flat(p0, 3)
+    a, b = Flat(p0, len(classes)), Flat(p0, len(classes))
     for t in range(2):
         g = (1e-2 * torch.randn(n, generator=gen)).to(DEV)
         gb = g.to(torch.bfloat16) if bf16_grad else None
@@ -175,12 +195,14 @@ def test_runs_one_launch_matches_per_run(grad_scale, bf16_grad):
     torch.cuda.synchronize()
     for x, y, name in zip(a.state(), b.state(), ("p", "exp_avg", "exp_avg_sq", "shadow", "counters")):
         assert torch.equal(x, y), name
-    assert b.counters.tolist() == [2, 2, 0]
+    assert b.counters.tolist() == counters
     assert torch.isfinite(b.p).all()
-    for s, e in ((9, 12), (12, 2059), (2059, 2060), (4109, 4112), (8211, n)):     # gaps and the gated-off run
+    for s, e in untouched:                                                        # gaps and the gated-off run
         assert torch.equal(b.p[s:e].cpu(), p0[s:e]) and not b.m[s:e].any() and not b.v[s:e].any()
-    assert not torch.equal(b.p[2060:4109].cpu(), p0[2060:4109])
-    assert torch.equal(b.s[4112:8211], b.p[4112:8211].to(torch.bfloat16))
+    s, e = changed
+    assert not torch.equal(b.p[s:e].cpu(), p0[s:e])
+    s, e = shadowed
+    assert torch.equal(b.s[s:e], b.p[s:e].to(torch.bfloat16))
 
 
 def _toy_store():

@@ -255,19 +255,35 @@ def test_sgd_data_parallel_fold(world):
             assert rel(buf, bref) < 1e-6 and rel(p, p0 - 0.1 * bref) < 1e-6
 
 
-@pytest.mark.parametrize("fold", [False, True])
-def test_sgd_runs_one_launch_matches_per_run(fold):
+def _ragged_five(off, on):
+    """(n, runs, untouched ranges, a range that must change)"""
+    runs = [(0, 5003, None, True), (5008, 5012, off, False), (5016, 30000, on, False), (30008, 30009, None, False),
+            (30016, 59999, None, True)]
+    return 60000, runs, ((5003, 5016), (30000, 30008), (30009, 30016), (59999, 60000)), (5016, 30000)
+
+
+def _full_table(off, on):
+    """Exactly 64 runs, the table's limit (its last slot, prefix[64], bit 63 of the first mask): 63 runs of lengths
+    cycling 1..9 at starts 12 r, then one of 2049 elements (two workgroups and a tail); first on runs 0, 31, 32 and
+    63, a closed gate on run 33, an open one on run 63."""
+    runs = [(12 * r, 12 * r + 1 + r % 9, off if r == 33 else None, r in (0, 31, 32)) for r in range(63)]
+    runs.append((756, 756 + 2049, on, True))
+    gaps = tuple((runs[r][1], runs[r + 1][0]) for r in range(63)) + ((runs[33][0], runs[33][1]), (2805, 2808))
+    return 2808, runs, gaps, (756, 2805)
+
+
+@pytest.mark.parametrize("fold,table", [(False, _ragged_five), (True, _ragged_five), (False, _full_table),
+                                        (True, _full_table)], ids=["False", "True", "64runs-False", "64runs-True"])
+def test_sgd_runs_one_launch_matches_per_run(fold, table):
     """dfk_sgd_step_runs (every run of the step in one launch, optim.FusedSGD's default) against one dfk_sgd_step
     per run, bit for bit: ragged run lengths (scalar tails, runs shorter than a workgroup), gaps between runs left
     untouched, a dropped (gate 0) and a kept (gate 1) LayerDrop run, first / later momentum, the bf16 shadow, and
-    the data-parallel fold (1 / world, bf16 bucket gradient)."""
+    the data-parallel fold (1 / world, bf16 bucket gradient); with five runs and with a full table of 64."""
     g = torch.Generator(device=DEV).manual_seed(7)
-    n = 60000
+    off, on = torch.zeros(1, device=DEV), torch.ones(1, device=DEV)
+    n, runs, untouched, changed = table(off, on)
     p0, g0, b0 = (torch.randn(n, device=DEV, generator=g) for _ in range(3))
     gb = (g0 * 3).to(torch.bfloat16) if fold else None
-    off, on = torch.zeros(1, device=DEV), torch.ones(1, device=DEV)
-    runs = [(0, 5003, None, True), (5008, 5012, off, False), (5016, 30000, on, False), (30008, 30009, None, False),
-            (30016, 59999, None, True)]
     scale = 1.0 / 3 if fold else 1.0
     pa, ba, sa = p0.clone(), b0.clone(), torch.zeros(n, device=DEV, dtype=torch.bfloat16)
     for s, e, gate, first in runs:
@@ -278,9 +294,10 @@ def test_sgd_runs_one_launch_matches_per_run(fold):
                     grad_bf16=gb)
     torch.cuda.synchronize()
     assert torch.equal(pa, pb) and torch.equal(ba, bb) and torch.equal(sa, sb)
-    for s, e in ((5003, 5016), (30000, 30008), (30009, 30016), (59999, n)):   # dropped run and gaps: untouched
+    for s, e in untouched:                                                    # dropped run and gaps: untouched
         assert torch.equal(pb[s:e], p0[s:e]) and torch.equal(bb[s:e], b0[s:e])
-    assert not torch.equal(pb[5016:30000], p0[5016:30000])
+    s, e = changed
+    assert not torch.equal(pb[s:e], p0[s:e])
 
 
 def test_fused_c1_regularized_step():

@@ -1,7 +1,7 @@
 // Host-side checks of libdfk under AddressSanitizer (CPU only; no kernel is launched).  Exercises the C ABI's
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
 // conv0, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
-// dims, the AdamW entry points' buffers / run table / hyper-parameters, the gradient-clipping entry points' slab /
+// dims, the SGD and AdamW entry points' buffers / run table / hyper-parameters, the gradient-clipping entry points' slab /
 // coefficient / max_norm / run table), which must return DFK_EINVAL before touching
 // the device.  Built and run by tools/asan/run.sh.
 #include <cstdio>
@@ -162,6 +162,29 @@ int main() {
                            nullptr, nullptr) != 0);
   EXPECT(dfk_sgd_step(nullptr, nullptr, nullptr, nullptr, 10, nullptr, 0.1f, 0.9f, 0.f, 0, nullptr, 1.f, nullptr,
                       nullptr) != 0);
+  {
+    // SGD: the run table, its limits and the alignment rules of dfk_sgd_step_runs (the rows AdamW has below)
+    float* fx = reinterpret_cast<float*>(0x10000);
+    float* odd = reinterpret_cast<float*>(0x10004);
+    int64_t runs[65 * 4];
+    for (int r = 0; r < 65; ++r) { runs[4 * r] = 64 * r; runs[4 * r + 1] = 40; runs[4 * r + 2] = 0; runs[4 * r + 3] = 0; }
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, nullptr, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, runs, 0, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, runs, -1, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, runs, 65, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_ENOTSUP);
+    runs[5] = 0;                                                           // an empty run
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    runs[5] = 40; runs[4] = -64;                                           // negative start
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    runs[4] = 66;                                                          // run start not a multiple of 4
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    runs[4] = 64;
+    EXPECT(dfk_sgd_step_runs(odd, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, odd, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, 0.f, 1.f, odd, nullptr) == DFK_EINVAL);
+    // the one-run entry point writes the shadow in 8-B quads too
+    EXPECT(dfk_sgd_step(fx, fx, fx, odd, 16, fx, 0.f, 0.9f, 0.f, 0, nullptr, 1.f, nullptr, nullptr) == DFK_EINVAL);
+  }
   {
     // AdamW: malformed calls return before any launch (fx: a fake 16-B aligned device pointer, never touched)
     float* fx = reinterpret_cast<float*>(0x10000);

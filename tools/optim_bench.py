@@ -7,8 +7,11 @@ HIP events on the op's stream around `inner` back-to-back calls, median over `re
 cases are timed interleaved in each repeat.  Gradient clipping: the norm pass (dfk_grad_sqnorm_runs +
 dfk_grad_clip_coef, 4 B per element, so 4/22 of the yardstick by the bytes model) alone, and FusedSGD.step /
 FusedAdamW.step with max_grad_norm on and off.  With --step also the C2 step level (graph-replayed TrainStep, B = 8,
-SGD and AdamW, each with clipping off and on), for orientation.  Prints one JSON line.
-Usage: python tools/optim_bench.py [reps] [inner] [--step]"""
+SGD and AdamW, each with clipping off and on), for orientation.  With --bits the line also carries a sha256 of every
+state buffer after the timed calls: the sequence of calls is fixed by reps / inner, the inputs are seeded and no
+kernel uses atomics, so two builds that compute the same thing print the same hashes.  Prints one JSON line.
+Usage: python tools/optim_bench.py [reps] [inner] [--step] [--bits]"""
+import hashlib
 import json
 import os
 import statistics
@@ -46,6 +49,10 @@ def interleaved(cases, reps, inner, warm=5):
         for k, fn in cases.items():
             ms[k].append(timed(fn, inner))
     return ms
+
+
+def sha256(t):
+    return hashlib.sha256(t.detach().contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
 
 
 def step_pair(reps, inner):
@@ -139,6 +146,12 @@ def main():
                             "adamw": round(med["FusedAdamW.step+clip"] - med["FusedAdamW.step"], 4)},
            "grad_norm_value": [round(v, 6) for v in adam_c.grad_norm.tolist()],
            "device": torch.cuda.get_device_name(0)}
+    if "--bits" in sys.argv:
+        torch.cuda.synchronize()
+        out["sha256"] = {k: sha256(t) for k, t in {
+            "store.flat": store.flat, "store.shadow": store.shadow, "sgd.buf": sgd.buf, "adam.exp_avg": adam.exp_avg,
+            "adam.exp_avg_sq": adam.exp_avg_sq, "adam.counters": adam.counters, "adam.corr": adam.corr,
+            "sgd+clip.grad_norm": sgd_c.grad_norm, "adam+clip.grad_norm": adam_c.grad_norm}.items()}
     if "--step" in sys.argv:
         del model, store, sgd, adam, sgd_c, adam_c, cases
         torch.cuda.empty_cache()
