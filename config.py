@@ -19,6 +19,10 @@
                            --adam_beta1, --adam_beta2, --adam_eps set its other hyper-parameters
   --clip_grad_norm FLOAT   global gradient-norm clipping (torch.nn.utils.clip_grad_norm_ on the mean gradient right
                            before the step) fused into either optimizer on the device; 0 (default): off
+  --ema_decay FLOAT        exponential moving average of the weights, updated on the device right after every
+                           optimizer step (inside the captured step); validation, submission and the checkpoint's
+                           "checkpoint_ema" use the averaged weights; 0 (default): off.  --ema_warmup ramps the decay
+                           as min(decay, (1 + n) / (10 + n)) over the first updates
   --video_encoder {swin,inception}   video slot: the north-star Video Swin 3D (default) or the reference's
                            current InceptionVideoClassifier (Inception-ResNet-v2 + NeXtVLAD, train.py:32,44)
 
@@ -96,6 +100,11 @@ def build_parser():
     parser.add_argument('--adam_eps', type=float, default=1e-8)
     parser.add_argument('--clip_grad_norm', type=float, default=0.0,
                         help='max global gradient norm (clip_grad_norm_ semantics, on the device); 0: no clipping')
+    parser.add_argument('--ema_decay', type=float, default=0.0,
+                        help='decay of the weight EMA kept on the device, in [0, 1) (e.g. 0.9999); validation, '
+                             'submission and the checkpoint use the averaged weights; 0: no EMA')
+    parser.add_argument('--ema_warmup', action='store_true',
+                        help='ramp the EMA decay as min(ema_decay, (1 + n) / (10 + n)) after n updates')
     return parser
 
 

@@ -134,6 +134,9 @@ SIGNATURES = {
                             _F, _VP, _VP],
     "dfk_grad_sqnorm_runs": [_VP, _VP, _VP, _I32, _F, _VP, _VP],
     "dfk_grad_clip_coef": [_VP, _I32, _F, _VP, _VP],
+    "dfk_ema_prelude": [_VP, _VP, C.c_double, _I32, _VP],
+    "dfk_ema_update": [_VP, _VP, _I64, _VP, _VP],
+    "dfk_ema_swap": [_VP, _VP, _VP, _I64, _VP],
     "dfk_im2col2d": [_VP, _I64, _VP, C.POINTER(Conv2dGeo), C.c_int, _VP],
     "dfk_col2im2d": [_VP, _VP, _I64, C.POINTER(Conv2dGeo), C.c_int, C.c_int, _VP],
     "dfk_bn2d_fwd": [_VP, _I64, _VP, _I64, _I64, _I32, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int,

@@ -658,6 +658,38 @@ def grad_clip_coef(partials, n, max_norm, out):
             "grad_clip_coef")
 
 
+def ema_prelude(num_updates, weight, decay, warmup=False):
+    """Once per step, before ema_update: t = num_updates[0]++ (device int32 [1]) and weight[0] (device fp32 [1]) =
+    1 - (min(decay, (1 + t) / (10 + t)) if warmup else decay), evaluated in double on the device."""
+    if num_updates.dtype != torch.int32 or weight.dtype != torch.float32 or num_updates.numel() != 1 \
+            or weight.numel() != 1:
+        raise ValueError("ema_prelude: num_updates is one device int32, weight one device fp32")
+    L.check(L.lib().dfk_ema_prelude(L.ptr(num_updates), L.ptr(weight), float(decay), int(bool(warmup)), L.stream()),
+            "ema_prelude")
+
+
+def _ema_pair(param, ema, what):
+    if param.dtype != torch.float32 or ema.dtype != torch.float32 or ema.numel() != param.numel() \
+            or not (param.is_contiguous() and ema.is_contiguous()):
+        raise ValueError(f"{what}: param and ema are contiguous fp32 buffers of one size")
+
+
+def ema_update(param, ema, weight):
+    """ema <- fma(w, param - ema, ema) over the whole buffer, w = weight[0] read on the device (ema_prelude's)."""
+    _ema_pair(param, ema, "ema_update")
+    if weight.dtype != torch.float32 or weight.numel() != 1:
+        raise ValueError("ema_update: weight is one device fp32 (ema_prelude's)")
+    L.check(L.lib().dfk_ema_update(L.ptr(param), L.ptr(ema), param.numel(), L.ptr(weight), L.stream()), "ema_update")
+
+
+def ema_swap(param, ema, shadow=None):
+    """param <-> ema, and shadow = bf16(new param) when a shadow is given; a second call undoes the first."""
+    _ema_pair(param, ema, "ema_swap")
+    if shadow is not None and (shadow.dtype != torch.bfloat16 or shadow.numel() != param.numel()):
+        raise ValueError("ema_swap: shadow is the bf16 buffer of param's size")
+    L.check(L.lib().dfk_ema_swap(L.ptr(param), L.ptr(ema), _opt(shadow), param.numel(), L.stream()), "ema_swap")
+
+
 def dropout(x, drop, out=None, group_rows=None):
     """out = x * mask / (1 - p) over a 2-D [rows, cols] view (out may be x)."""
     rows, cols = x.shape

@@ -10,7 +10,11 @@ graph takes the right bias corrections.
 max_grad_norm (both): torch.nn.utils.clip_grad_norm_(params, max_grad_norm) on the mean gradient right before the
 step, on the device: one reduction pass over the step's runs, a one-workgroup coefficient kernel, and update
 kernels that multiply the gradient by the coefficient they read from device memory.
+ParamEMA: an exponential moving average of the whole flat store, updated by one kernel right after the optimizer step
+(its update count and decay warm-up in device memory, so it replays inside the captured step) and exchanged with the
+live weights for evaluation, so the model itself evaluates through the average ("Weight EMA").
 """
+import contextlib
 import math
 import os
 
@@ -199,6 +203,96 @@ class FusedAdamW(_Fused):
         self.active = list(sd["active"]) if sd["active"] is not None else None
         self.param_groups[0]["initial_lr"] = self.base_lr
         self.set_lr(sd["lr"])
+
+
+class ParamEMA:
+    """Exponential moving average of every parameter of a ParamStore: e <- e + w (p - e), w = 1 - decay, over the
+    whole flat fp32 buffer (timm.ModelEmaV2 / swa_utils.AveragedModel semantics: every parameter every step, also one
+    the optimizer skipped — a LayerDrop-dropped layer, a grad=None head; alignment and group gaps hold 0 and stay 0).
+
+    update() is two launches, both capturable: the prelude advances the device count num_updates (int32 [1]) and
+    writes this step's w into `weight` (fp32 [1]); with warmup the decay is min(decay, (1 + t) / (10 + t)) after t
+    updates, so a short fine-tune at decay 0.9999 leaves its initial copy.  Then one pass over the store.
+    swap() exchanges the average with the live weights in place (flat, and the bf16 shadow rewritten from the new
+    flat), so the existing model evaluates through the average with no second module; applied() is the context
+    manager around an evaluation and restores the live weights bit for bit, also when its body raises.
+    Buffers (BatchNorm running statistics, ...) are not parameters and are not averaged: evaluation under applied()
+    uses the live ones.
+    Data parallel: built after the rank-0 parameter broadcast, every rank applies the same deterministic update to
+    identical bytes, so the replicas' averages stay bit-equal with no collective."""
+
+    def __init__(self, store, decay, warmup=False):
+        decay = float(decay)
+        if not (math.isfinite(decay) and 0.0 <= decay < 1.0):
+            raise ValueError(f"ParamEMA: decay must lie in [0, 1), got {decay}")
+        self.store, self.decay, self.warmup = store, decay, bool(warmup)
+        dev = store.flat.device
+        self.ema = store.flat.clone()
+        self.num_updates = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.weight = torch.zeros(1, device=dev, dtype=torch.float32)
+        self.swapped = False   # True while the store holds the average (between the two swaps of applied())
+
+    def _live(self, what):
+        if self.swapped:
+            raise RuntimeError(f"ParamEMA.{what}: the store holds the averaged weights (inside applied() / after an "
+                               f"odd number of swap() calls)")
+
+    def reset(self):
+        """Restart the average from the store's current weights (e.g. after a checkpoint was loaded into them)."""
+        self._live("reset")
+        self.ema.copy_(self.store.flat)
+        self.num_updates.zero_()
+
+    def update(self):
+        """One EMA update from the store's current weights; call right after optimizer.step()."""
+        self._live("update")
+        K.ema_prelude(self.num_updates, self.weight, self.decay, self.warmup)
+        K.ema_update(self.store.flat, self.ema, self.weight)
+
+    def swap(self):
+        """Exchange the average and the live weights (and rewrite the bf16 shadow); a second call undoes it."""
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ParamEMA.swap: not during a graph capture (a replay would swap again)")
+        K.ema_swap(self.store.flat, self.ema, self.store.shadow)
+        self.swapped = not self.swapped
+
+    @contextlib.contextmanager
+    def applied(self):
+        """Inside, the model's parameters (and store.shadow) are the averaged weights; on exit the live weights are
+        back bit for bit.  Not re-entrant: a nested applied() raises instead of silently un-swapping."""
+        self._live("applied")
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def named_tensors(self, model):
+        """{parameter name: view of the average} with the model's own state_dict keys and shapes (the parameters the
+        store holds; frozen ones are not averaged and are absent)."""
+        self._live("named_tensors")
+        st, out = self.store, {}
+        for name, p in model.named_parameters():
+            i = st.index.get(id(p))
+            if i is not None:
+                s, e = st.span(i)
+                out[name] = self.ema[s:e].view(p.shape)
+        return out
+
+    def state_dict(self):
+        self._live("state_dict")
+        return {"ema": self.ema, "num_updates": self.num_updates, "decay": self.decay, "warmup": self.warmup}
+
+    def load_state_dict(self, sd):
+        self._live("load_state_dict")
+        if sd["ema"].numel() != self.ema.numel() or sd["num_updates"].numel() != 1:
+            raise ValueError("ParamEMA.load_state_dict: state of another parameter store")
+        decay = float(sd["decay"])
+        if not (math.isfinite(decay) and 0.0 <= decay < 1.0):
+            raise ValueError(f"ParamEMA.load_state_dict: decay must lie in [0, 1), got {decay}")
+        self.ema.copy_(sd["ema"])
+        self.num_updates.copy_(sd["num_updates"])
+        self.decay, self.warmup = decay, bool(sd["warmup"])
 
 
 class CosineAnnealingLR:

@@ -8,7 +8,9 @@ re-built MI355X-first:
 * parameters / gradients in flat buffers with a bf16 compute shadow
   (deepfake_amd.params), fused SGD(momentum 0.9, weight decay), or with
   --optimizer adamw fused AdamW (src/trainer.py:6,78), + CosineAnnealingLR
-  (src/trainer.py:80-85) with the lr in device memory;
+  (src/trainer.py:80-85) with the lr in device memory; with --ema_decay an
+  exponential moving average of the weights updated on the device after every
+  optimizer step, which validation, submission and the checkpoint then use;
 * BCELoss on the sigmoid output (src/trainer.py:88,132), accuracy
   (prob >= 0.5) == label (:142-144), gradient accumulation over accum_step
   micro-batches with the all-reduce only on the last one (:280-297);
@@ -16,6 +18,7 @@ re-built MI355X-first:
   step at :133,136);
 * optional HIP-graph capture of the whole step (TrainStep(graph=True)).
 """
+import contextlib
 import math
 import os
 import time
@@ -25,7 +28,7 @@ import torch.distributed as dist
 
 from . import rng
 from .ddp import GradBucketer, fr_last_id, recorder_on
-from .optim import CosineAnnealingLR, FusedAdamW, FusedSGD
+from .optim import CosineAnnealingLR, FusedAdamW, FusedSGD, ParamEMA
 from .params import ParamStore
 from .utils import AverageMeter, Logger
 
@@ -80,6 +83,16 @@ def clip_arg(args):
     if not math.isfinite(clip) or clip < 0:
         raise ValueError(f"--clip_grad_norm must be a positive finite number (0: off), got {clip}")
     return clip if clip > 0 else None
+
+
+def ema_arg(args):
+    """--ema_decay as ParamEMA's decay: None for 0 / absent (off), the value in (0, 1) otherwise; a value outside
+    [0, 1) or non-finite is an error, not a silent "off"."""
+    decay = getattr(args, "ema_decay", None)
+    decay = 0.0 if decay is None else float(decay)
+    if not math.isfinite(decay) or not 0.0 <= decay < 1.0:
+        raise ValueError(f"--ema_decay must lie in [0, 1) (0: off), got {decay}")
+    return decay if decay > 0 else None
 
 
 def check_grad_norm(norm, step):
@@ -153,10 +166,12 @@ class TrainStep:
     non-final ones run under the bucketer's no_sync() (no all-reduce), the final
     one launches the overlapped bucket all-reduces over the accumulated sum, then
     the optimizer step and zero_grad.  BatchNorm running statistics are re-broadcast from rank 0
-    at the first micro-step of every optimizer step (§8e)."""
+    at the first micro-step of every optimizer step (§8e).
+    ema (optim.ParamEMA, optional): its update follows every optimizer step, eagerly and inside the step graphs."""
 
-    def __init__(self, model, store, opt, bucketer, graph=False, parallel_branches=True):
+    def __init__(self, model, store, opt, bucketer, graph=False, parallel_branches=True, ema=None):
         self.model, self.store, self.opt, self.bucketer = model, store, opt, bucketer
+        self.ema = ema
         if parallel_branches and hasattr(model, "parallel_branches") and torch.cuda.is_available() \
                 and store.flat.is_cuda:
             model.parallel_branches = True
@@ -201,6 +216,8 @@ class TrainStep:
         fold = self._fold()
         fa = self.bucketer.finish(fold=fold)   # overlapped bucket all-reduces (hooks); the optimizer takes the mean
         self.opt.step(**fa)             # FusedSGD: the first call initialises the momentum buffer (torch semantics)
+        if self.ema is not None:
+            self.ema.update()
         self.store.zero_grad()
         self.first_micro = True
         # detach: a live autograd graph would pin AccumulateGrad nodes to this stream (breaks capture)
@@ -359,6 +376,8 @@ class TrainStep:
             else:
                 fa = self.bucketer.allreduce_all(fold=fold)
             self.opt.step(first=False, **fa)
+            if self.ema is not None:
+                self.ema.update()
             if accum > 1:                      # the next window starts from zero gradients and gates
                 self.store.grad.zero_()
                 self.store.zero_gates()
@@ -457,14 +476,22 @@ class Trainer:
                                       max_grad_norm=clip)
         steps_per_epoch = max(1, int(len(self.trainloader) / self.accum_step))
         self.scheduler = CosineAnnealingLR(self.optimizer, T_max=self.train_epochs * steps_per_epoch)
-        self.step_fn = TrainStep(model, self.store, self.optimizer, self.bucketer, graph=graph)
+        # the weight EMA starts after the rank-0 broadcast above: identical bytes and one deterministic update on
+        # every rank keep the replicas' averages bit-equal with no collective
+        decay = ema_arg(args)
+        self.ema = ParamEMA(self.store, decay, warmup=bool(getattr(args, "ema_warmup", False))) \
+            if decay is not None else None
+        self.step_fn = TrainStep(model, self.store, self.optimizer, self.bucketer, graph=graph, ema=self.ema)
         self.lossF = torch.nn.BCELoss()
         n = sum(p.numel() for p in model.parameters())
         self.logger(f"model params: {n / 1e6:.3f} M ({n * 4 / 2 ** 20:.1f} MiB fp32)")
 
     def load_ckpt(self, args):
         """src/trainer.py:90-122: {'checkpoint': state_dict} with strict=False and
-        'module.' stripping for single-modality runs; optimizer/epoch not restored."""
+        'module.' stripping for single-modality runs; optimizer/epoch not restored.
+        With the weight EMA on, the file's "ema" state is restored when it belongs to a store of this size (the
+        decay and warm-up stay those of this run's flags); otherwise the average restarts from the loaded weights,
+        never from the initialisation they replaced."""
         path = args.fused_ckpt_path if self.modality == "fused" else (
             args.audio_ckpt_path if self.modality == "audio" else args.video_ckpt_path)
         ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -473,12 +500,33 @@ class Trainer:
             sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
         self.model_s.load_state_dict(sd, strict=False)
         self.store.refresh_shadow()
+        if self.ema is not None:
+            es = ck.get("ema")
+            if isinstance(es, dict) and torch.is_tensor(es.get("ema")) and es["ema"].numel() == self.ema.ema.numel():
+                decay, warmup = self.ema.decay, self.ema.warmup
+                self.ema.load_state_dict(es)
+                self.ema.decay, self.ema.warmup = decay, warmup
+                self.logger("Load EMA Weights Succesfully")
+            else:
+                self.ema.reset()
         self.logger("Load Finetuned Model Succesfully")
 
     def save_ckpt(self, path, epoch):
+        """{'epoch', 'checkpoint', 'optimizer'}; with the weight EMA on also 'checkpoint_ema', a state_dict-shaped
+        dict (the averaged parameters under the model's own keys, the live buffers beside them) that a loader can
+        take in place of 'checkpoint', and 'ema', the ParamEMA state."""
         if self.rank == 0:
-            torch.save({"epoch": epoch, "checkpoint": self.model_s.state_dict(),
-                        "optimizer": self.optimizer.state_dict()}, path)
+            sd = self.model_s.state_dict()
+            ck = {"epoch": epoch, "checkpoint": sd, "optimizer": self.optimizer.state_dict()}
+            if self.ema is not None:
+                avg = self.ema.named_tensors(self.model_s)
+                ck["checkpoint_ema"] = type(sd)((k, avg.get(k, v)) for k, v in sd.items())
+                ck["ema"] = self.ema.state_dict()
+            torch.save(ck, path)
+
+    def _averaged(self):
+        """The context of an evaluation: inside, the model's parameters are the EMA weights (when EMA is on)."""
+        return self.ema.applied() if self.ema is not None else contextlib.nullcontext()
 
     def _features(self, feat):
         """src/trainer.py:250-262: the batch's features on the device, waveforms padded to the longest and
@@ -504,7 +552,7 @@ class Trainer:
         dataloader = dataloader or self.dataset.test_dataloader()
         self.model.eval()
         res = {}
-        with torch.no_grad(), open(path, "a") as f:
+        with torch.no_grad(), self._averaged(), open(path, "a") as f:
             for iter_id, (feat, names) in enumerate(dataloader):
                 out = self.model(self._features(feat)).float().reshape(-1).cpu()
                 for name, v in zip(names, out.numpy()):
@@ -528,13 +576,14 @@ class Trainer:
     def eval(self, dataloader, epoch, t, lr, val_loss_draw=None, gpu_log=None):
         stat = AverageMeter()
         self.model.eval()
-        with torch.no_grad():
+        tag = "Val(EMA)" if self.ema is not None else "Val"   # validation runs on the averaged weights when EMA is on
+        with torch.no_grad(), self._averaged():
             for batch in dataloader:
                 feature, label = self._prep(batch)
                 r = self.run_batch(feature, label)
                 if t % self.log_step == 0:
-                    self.logger("| epoch {:2d} | step {:4d} | lr {:.4E} | Val Loss {:3.5f} | Val Acc {:1.5f} ".format(
-                        epoch, t, lr, r["loss"].item(), r["acc"].item()))
+                    self.logger("| epoch {:2d} | step {:4d} | lr {:.4E} | {} Loss {:3.5f} | Val Acc {:1.5f} ".format(
+                        epoch, t, lr, tag, r["loss"].item(), r["acc"].item()))
                 stat.update(r["loss"].item())
                 t += 1
         self.logger(f"Phase:val, Avg Loss:{stat.avg}")

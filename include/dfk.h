@@ -458,6 +458,26 @@ int dfk_adamw_step_runs_clip(float* param, const float* grad, float* exp_avg, fl
                              float eps, float weight_decay, const float* corr, int32_t nclass, float grad_scale,
                              const void* grad_bf16, const float* clip_coef, hipStream_t stream);
 
+/* Exponential moving average of the weights (csrc/ema.hip): one more flat fp32 buffer `ema` over the parameter
+ * store, updated right after the optimizer step, inside the same captured graph, with no host involvement.
+ * dfk_ema_prelude, once per step ahead of the update (one workgroup, one thread acts): t = (*num_updates)++ is the
+ *   number of updates done before this one; d = warmup ? min(decay, (1 + t) / (10 + t)) : decay, evaluated in double
+ *   (the ramp of TensorFlow's ExponentialMovingAverage(num_updates=)); *weight = (float)(1 - d).  num_updates: device
+ *   int32 [1], weight: device fp32 [1], so a replayed graph advances the count.  DFK_EINVAL for decay outside [0, 1)
+ *   or not finite.
+ * dfk_ema_update: e <- fma(w, p - e, e) per element over [0, n) with w = *weight (device): the subtraction rounded
+ *   once, then one fma; w == 1 (decay 0) is the exact copy e = p, as torch.lerp at weight 1 (the rounded (p - e) + e
+ *   need not return p).  Meant for the WHOLE store, alignment and group gaps included (p = 0, e = 0 stays 0), so that
+ *   parameters the optimizer skipped in this step are averaged too.  param is only read.  12 B per element.
+ * dfk_ema_swap: param[i] <-> ema[i], and bf16_shadow[i] = bf16(new param[i]) when bf16_shadow != NULL.  Two calls
+ *   restore param, ema and the shadow bit for bit wherever shadow == bf16(param) held before the first.
+ * The fp32 pointers (param, ema, weight) 16-B aligned, param and ema distinct, bf16_shadow 8-B aligned, num_updates
+ * 4-B aligned; DFK_EINVAL otherwise, before any device work.
+ * n == 0 is a no-op.  Nothing is allocated and nothing read on the host. */
+int dfk_ema_prelude(int32_t* num_updates, float* weight, double decay, int32_t warmup, hipStream_t stream);
+int dfk_ema_update(const float* param, float* ema, int64_t n, const float* weight, hipStream_t stream);
+int dfk_ema_swap(float* param, float* ema, void* bf16_shadow, int64_t n, hipStream_t stream);
+
 /* y = x * mask / (1 - p) over [rows, cols] (row stride ld; y may alias x): nn.Dropout / DropPath as a
  * standalone pass, and the backward of every fused dropout site (the same mask applied to the gradient). */
 int dfk_dropout(const void* x, void* y, int64_t rows, int32_t cols, int64_t ld, const dfk_drop* drop, int dtype,

@@ -2,10 +2,11 @@
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
 // conv0, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
 // dims, the SGD and AdamW entry points' buffers / run table / hyper-parameters, the gradient-clipping entry points' slab /
-// coefficient / max_norm / run table), which must return DFK_EINVAL before touching
+// coefficient / max_norm / run table, the weight-EMA entry points' buffers / decay), which must return DFK_EINVAL before touching
 // the device.  Built and run by tools/asan/run.sh.
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/dfk.h"
 
@@ -319,6 +320,39 @@ int main() {
                                     nullptr, fx, nullptr) == DFK_EINVAL);
     EXPECT(dfk_adamw_step_runs_clip(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
                                     odd, fx, nullptr) == DFK_EINVAL);      // grad_bf16 not 8-B aligned
+  }
+  {
+    // weight EMA: the prelude, the update and the swap reject malformed calls; an empty buffer is a no-op
+    float* fx = reinterpret_cast<float*>(0x10000);
+    float* fy = reinterpret_cast<float*>(0x20000);
+    float* odd = reinterpret_cast<float*>(0x10004);
+    int32_t* cnt = reinterpret_cast<int32_t*>(0x30000);
+    void* sh = reinterpret_cast<void*>(0x40000);
+    const double inf = 1.0 / 0.0, nan = inf - inf;
+    EXPECT(dfk_ema_prelude(nullptr, fx, 0.9, 0, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_prelude(cnt, nullptr, 0.9, 0, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_prelude(cnt, odd, 0.9, 0, nullptr) == DFK_EINVAL);                     // weight not 16-B aligned
+    EXPECT(dfk_ema_prelude(reinterpret_cast<int32_t*>(0x30002), fx, 0.9, 0, nullptr) == DFK_EINVAL);
+    for (double bad : {-0.1, 1.0, 1.5, inf, -inf, nan}) EXPECT(dfk_ema_prelude(cnt, fx, bad, 1, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(nullptr, fy, 16, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(fx, nullptr, 16, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(fx, fy, 16, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(fx, fx, 16, fy, nullptr) == DFK_EINVAL);                        // param and ema alias
+    EXPECT(dfk_ema_update(fx, fy, -4, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(odd, fy, 16, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(fx, odd, 16, fy, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(fx, fy, 16, odd, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_update(fx, fy, (int64_t)1 << 43, fx, nullptr) == DFK_EINVAL);          // grid beyond int32
+    EXPECT(dfk_ema_update(fx, fy, 0, fx, nullptr) == 0);
+    EXPECT(dfk_ema_swap(nullptr, fy, sh, 16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_swap(fx, nullptr, sh, 16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_swap(fx, fx, sh, 16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_swap(fx, fy, sh, -4, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_swap(odd, fy, sh, 16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_swap(fx, odd, nullptr, 16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_swap(fx, fy, odd, 16, nullptr) == DFK_EINVAL);                         // shadow not 8-B aligned
+    EXPECT(dfk_ema_swap(fx, fy, nullptr, (int64_t)1 << 43, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_ema_swap(fx, fy, nullptr, 0, nullptr) == 0);
   }
   EXPECT(dfk_cpb_bias_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 169, 512, 64, nullptr) != 0);
   std::printf("host_check: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);

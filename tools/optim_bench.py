@@ -7,7 +7,10 @@ HIP events on the op's stream around `inner` back-to-back calls, median over `re
 cases are timed interleaved in each repeat.  Gradient clipping: the norm pass (dfk_grad_sqnorm_runs +
 dfk_grad_clip_coef, 4 B per element, so 4/22 of the yardstick by the bytes model) alone, and FusedSGD.step /
 FusedAdamW.step with max_grad_norm on and off.  With --step also the C2 step level (graph-replayed TrainStep, B = 8,
-SGD and AdamW, each with clipping off and on), for orientation.  With --bits the line also carries a sha256 of every
+SGD and AdamW, each with clipping off and on, and SGD with the weight EMA on), for orientation.  Weight EMA:
+ema_update (dfk_ema_prelude + dfk_ema_update over the whole store: p read, e read and written, 12 B per element, 12/22
+of the yardstick by the bytes model) and ema_swap (dfk_ema_swap: p and e read and written, the shadow written, 18 B
+per element).  With --bits the line also carries a sha256 of every
 state buffer after the timed calls: the sequence of calls is fixed by reps / inner, the inputs are seeded and no
 kernel uses atomics, so two builds that compute the same thing print the same hashes.  Prints one JSON line.
 Usage: python tools/optim_bench.py [reps] [inner] [--step] [--bits]"""
@@ -22,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepfake_amd import kernels as K  # noqa: E402
 from deepfake_amd.models.fused import CONFIGS, build_fused  # noqa: E402
-from deepfake_amd.optim import FusedAdamW, FusedSGD  # noqa: E402
+from deepfake_amd.optim import FusedAdamW, FusedSGD, ParamEMA  # noqa: E402
 from deepfake_amd.params import ParamStore  # noqa: E402
 
 HBM_PEAK = 8e12   # bytes / s
@@ -62,7 +65,7 @@ def step_pair(reps, inner):
     from deepfake_amd.trainer import TrainStep
     cfg, dev = CONFIGS["c2"], torch.device("cuda")
     steps = {}
-    for name in ("sgd", "sgd+clip", "adamw", "adamw+clip"):
+    for name in ("sgd", "sgd+clip", "adamw", "adamw+clip", "sgd+ema"):
         clip = 1.0 if name.endswith("+clip") else None
         torch.manual_seed(1234)
         rng.manual_seed(1234, 0)
@@ -75,7 +78,8 @@ def step_pair(reps, inner):
                 torch.randn(8, 3, 224, 224, device=dev, generator=g),
                 torch.randn(8, int(16000 * cfg["seconds"]), device=dev, generator=g))
         label = (torch.rand(8, device=dev, generator=g) < 0.5).float()
-        ts = TrainStep(model, store, opt, GradBucketer(store), graph=True)
+        ema = ParamEMA(store, 0.9999, warmup=True) if name.endswith("+ema") else None
+        ts = TrainStep(model, store, opt, GradBucketer(store), graph=True, ema=ema)
         ts(feat, label)
         if ts.graph is None:
             raise SystemExit(f"optim_bench: the {name} step was not captured")
@@ -114,6 +118,11 @@ def main():
 
     def grad_norm():
         K.grad_clip_coef(part, K.grad_sqnorm_runs(store.grad, norm_tab, part), 1.0, pair)
+    ema = ParamEMA(store, 0.9999, warmup=True)
+
+    def ema_update():
+        K.ema_prelude(ema.num_updates, ema.weight, ema.decay, ema.warmup)
+        K.ema_update(store.flat, ema.ema, ema.weight)
     K.adamw_prelude(adam.counters, adam.corr, [(c, g) for c, g in enumerate(adam.gates)], b1, b2)
     cases = {
         "sgd_step_runs": lambda: K.sgd_step_runs(store.flat, store.grad, sgd.buf, store.shadow, sgd_tab, 0.9, 1e-3,
@@ -126,24 +135,33 @@ def main():
         "FusedSGD.step": sgd.step,
         "FusedSGD.step+clip": sgd_c.step,
         "FusedAdamW.step+clip": adam_c.step,
+        "ema_update": ema_update,
+        "ema_swap": lambda: K.ema_swap(store.flat, ema.ema, store.shadow),
     }
     ms = interleaved(cases, reps, inner)
     med = {k: statistics.median(v) for k, v in ms.items()}
     bytes_per = {"sgd_step_runs": 22, "adamw_step_runs": 30, "FusedAdamW.step": 30, "grad_norm": 4,
-                 "FusedSGD.step": 22, "FusedSGD.step+clip": 26, "FusedAdamW.step+clip": 34}
+                 "FusedSGD.step": 22, "FusedSGD.step+clip": 26, "FusedAdamW.step+clip": 34, "ema_update": 12,
+                 "ema_swap": 18}
+    elems = {k: store.numel if k.startswith("ema_") else n for k in med}   # the EMA kernels cover the gaps too
     out = {"config": "c2", "elements": n, "store_elements": store.numel, "runs": len(runs),
            "classes": len(adam.gates), "reps": reps, "inner": inner,
            "ms_median": {k: round(v, 4) for k, v in med.items()},
            "ms_min": {k: round(min(v), 4) for k, v in ms.items()},
            "ms_max": {k: round(max(v), 4) for k, v in ms.items()},
-           "TB_per_s": {k: round(bytes_per[k] * n / (med[k] * 1e-3) / 1e12, 3) for k in med},
-           "fraction_of_8TBps": {k: round(bytes_per[k] * n / (med[k] * 1e-3) / HBM_PEAK, 3) for k in med},
+           "TB_per_s": {k: round(bytes_per[k] * elems[k] / (med[k] * 1e-3) / 1e12, 3) for k in med},
+           "fraction_of_8TBps": {k: round(bytes_per[k] * elems[k] / (med[k] * 1e-3) / HBM_PEAK, 3) for k in med},
            "adamw_over_sgd": round(med["adamw_step_runs"] / med["sgd_step_runs"], 4), "bytes_ratio": round(30 / 22, 4),
            "prelude_ms": round(med["FusedAdamW.step"] - med["adamw_step_runs"], 4),
            "grad_norm_over_sgd": round(med["grad_norm"] / med["sgd_step_runs"], 4), "grad_norm_bytes_ratio": round(4 / 22, 4),
            "grad_norm_over_bytes_model": round(med["grad_norm"] / (med["sgd_step_runs"] * 4 / 22), 3),
            "clip_cost_ms": {"sgd": round(med["FusedSGD.step+clip"] - med["FusedSGD.step"], 4),
                             "adamw": round(med["FusedAdamW.step+clip"] - med["FusedAdamW.step"], 4)},
+           "ema_update_over_sgd": round(med["ema_update"] / med["sgd_step_runs"], 4),
+           "ema_update_over_bytes_model": round(med["ema_update"] / (med["sgd_step_runs"] * 12 / 22), 3),
+           "ema_swap_over_sgd": round(med["ema_swap"] / med["sgd_step_runs"], 4),
+           "ema_swap_over_bytes_model": round(med["ema_swap"] / (med["sgd_step_runs"] * 18 / 22), 3),
+           "ema_num_updates": int(ema.num_updates),
            "grad_norm_value": [round(v, 6) for v in adam_c.grad_norm.tolist()],
            "device": torch.cuda.get_device_name(0)}
     if "--bits" in sys.argv:
@@ -151,9 +169,10 @@ def main():
         out["sha256"] = {k: sha256(t) for k, t in {
             "store.flat": store.flat, "store.shadow": store.shadow, "sgd.buf": sgd.buf, "adam.exp_avg": adam.exp_avg,
             "adam.exp_avg_sq": adam.exp_avg_sq, "adam.counters": adam.counters, "adam.corr": adam.corr,
-            "sgd+clip.grad_norm": sgd_c.grad_norm, "adam+clip.grad_norm": adam_c.grad_norm}.items()}
+            "sgd+clip.grad_norm": sgd_c.grad_norm, "adam+clip.grad_norm": adam_c.grad_norm, "ema.ema": ema.ema,
+            "ema.num_updates": ema.num_updates}.items()}
     if "--step" in sys.argv:
-        del model, store, sgd, adam, sgd_c, adam_c, cases
+        del model, store, sgd, adam, sgd_c, adam_c, ema, cases
         torch.cuda.empty_cache()
         out["c2_step_ms"] = step_pair(max(reps // 3, 3), max(inner // 2, 5))
     print(json.dumps(out), flush=True)
