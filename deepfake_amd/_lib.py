@@ -95,6 +95,7 @@ _VP, _I64, _I32, _F = C.c_void_p, C.c_int64, C.c_int32, C.c_float
 SIGNATURES = {
     "dfk_gemm": [C.POINTER(GemmArgs), _VP],
     "dfk_gemm_workspace": [C.POINTER(GemmArgs)],
+    "dfk_gemm_dw_group": [C.POINTER(GemmArgs), _I32, _VP],
     "dfk_colsum": [_VP, C.c_int, _I64, _I64, _I64, _VP, _VP],
     "dfk_gemm_mx": [C.POINTER(GemmArgs), C.POINTER(MxOperand), C.POINTER(MxOperand), _VP],
     "dfk_mx_quant": [_VP, C.c_int, _I64, _I64, _I64, C.c_int, _VP, _I64, _VP, _VP],

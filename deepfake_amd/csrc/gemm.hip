@@ -621,9 +621,11 @@ __host__ __device__ __forceinline__ long view_extent(const dfk_view& v, long row
 // atomics (the same-address atomics serialise only when many splits add; below this, one more launch costs more)
 constexpr int kRsPartialMin = 32;
 
-template <int WT, int NWM, int NWN, bool AK, bool BKM, int S, bool RS, bool CONV = false>
-__global__ __launch_bounds__(NWM * NWN * 64) void gemm_dma_kernel(const dfk_gemm_args g, int kchunk, int evec,
-                                                                  SplitK sk) {
+// The kernel body for workgroup `bid` of a `grid`-shaped launch: gemm_dma_kernel passes blockIdx / gridDim, the
+// grouped weight-gradient kernel (below) the coordinates it decoded for one of its problems.
+template <int WT, int NWM, int NWN, bool AK, bool BKM, int S, bool RS, bool CONV>
+__device__ __forceinline__ void gemm_dma_body(const dfk_gemm_args& g, int kchunk, int evec, SplitK sk, const dim3 bid,
+                                              const dim3 grid) {
   constexpr int NWV = NWM * NWN, BM = NWM * WT, BN = NWN * WT, MI = WT / 16, BK = 64;
   constexpr int STAGE = (BM + BN) * BK;                         // elements per LDS stage
   constexpr int ES = WT + 4;
@@ -635,23 +637,23 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_dma_kernel(const dfk_gemm
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / NWN, wn = wave % NWN;
   int tn, tmi, z;
-  const int nwg = gridDim.x * gridDim.y;
-  if (g.atomic && g.splitk % 8 == 0 && (int)gridDim.z == g.splitk && nwg > 1) {
+  const int nwg = grid.x * grid.y;
+  if (g.atomic && g.splitk % 8 == 0 && (int)grid.z == g.splitk && nwg > 1) {
     // atomic split-K weight gradients: all nwg output tiles of one split on one XCD (the dispatcher deals
     // workgroups of the linear order to the 8 XCDs round robin), so the token range of the operand every tile
     // of that split reads (x: the whole narrow dW row block) comes from that XCD's L2 after the first tile
-    const int lin = blockIdx.z * nwg + blockIdx.y * gridDim.x + blockIdx.x;
+    const int lin = bid.z * nwg + bid.y * grid.x + bid.x;
     const int j = lin >> 3, i = j % nwg;
     z = (j / nwg) * 8 + (lin & 7);
-    tn = i % gridDim.x;
-    tmi = i / gridDim.x;
+    tn = i % grid.x;
+    tmi = i / grid.x;
   } else {
-    const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-    const int nid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-    tn = nid % gridDim.x;
-    tmi = nid / gridDim.x;
-    z = blockIdx.z;
+    const int b2 = bid.y * grid.x + bid.x;
+    const int xcd = b2 & 7, q = nwg >> 3, rr = nwg & 7;
+    const int nid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (b2 >> 3);
+    tn = nid % grid.x;
+    tmi = nid / grid.x;
+    z = bid.z;
   }
   const int bn = tn * BN, bm = tmi * BM;
   const int split = z % g.splitk;
@@ -759,7 +761,67 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_dma_kernel(const dfk_gemm
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
   tile_epilogue<bf16raw, WT>(g, smem_f, acc, lane, wave, wm, wn, bm, bn, z, split,
-                             (z * (int)gridDim.y + tmi) * (int)gridDim.x + tn, evec, sk);
+                             (z * (int)grid.y + tmi) * (int)grid.x + tn, evec, sk);
+}
+
+template <int WT, int NWM, int NWN, bool AK, bool BKM, int S, bool RS, bool CONV = false>
+__global__ __launch_bounds__(NWM * NWN * 64) void gemm_dma_kernel(const dfk_gemm_args g, int kchunk, int evec,
+                                                                  SplitK sk) {
+  gemm_dma_body<WT, NWM, NWN, AK, BKM, S, RS, CONV>(g, kchunk, evec, sk, blockIdx, gridDim);
+}
+
+// Grouped weight gradients (dfk_gemm_dw_group): up to kDwGroupMax independent dW problems of one tile shape in one
+// launch.  Each problem keeps the grid it has when launched alone (tile shape, split count, k order, XCD tile
+// order); the launch is their grids laid end to end, each padded to a multiple of 8 workgroups so that a
+// workgroup's position in its own problem falls on the same XCD as when launched alone.  The table travels by
+// value in the kernel arguments (like optim.hip's run tables), so a captured graph holds no table pointer.
+constexpr int kDwGroupMax = 8;
+struct DwProblem {
+  const void *a, *b;      // dy [K][M] view (k-major A) and x [K][N] view (k-major B), bf16
+  float *c, *rowsum;      // dW [M][N] fp32 (+=), optional db [M] (+=)
+  int32_t M, N, K;
+  int32_t lda, ldb, ldc;
+  int32_t splitk, kchunk;   // splitk > 1: atomic partials
+  int32_t gx, gy;           // the problem's own grid (gz = splitk)
+};
+struct DwGroup {
+  DwProblem p[kDwGroupMax];
+  int32_t prefix[kDwGroupMax + 1];   // first workgroup of each problem (multiples of 8); prefix[n] = the grid
+  int32_t n;
+};
+static_assert(sizeof(DwGroup) + 64 <= 4096, "the problem table must fit the kernel-argument block");
+
+template <int WT, bool RS>
+__global__ __launch_bounds__(256) void gemm_dw_group_kernel(const DwGroup T) {
+  const int b = blockIdx.x;
+  int pi = 0;
+#pragma unroll
+  for (int i = 1; i < kDwGroupMax; ++i) pi += (i < T.n && b >= T.prefix[i]) ? 1 : 0;
+  pi = __builtin_amdgcn_readfirstlane(pi);
+  const DwProblem& P = T.p[pi];
+  const int local = __builtin_amdgcn_readfirstlane(b - T.prefix[pi]);
+  const int gx = P.gx, gy = P.gy, gz = P.splitk;
+  if (local >= gx * gy * gz) return;   // padding to the next multiple of 8
+  dfk_gemm_args g{};
+  g.a.ptr = P.a;
+  g.a.ld = P.lda;
+  g.b.ptr = P.b;
+  g.b.ld = P.ldb;
+  g.c = P.c;
+  g.ldc = P.ldc;
+  g.M = P.M;
+  g.N = P.N;
+  g.K = P.K;
+  g.dtype = DFK_BF16;
+  g.a_kmajor = g.b_kmajor = g.c_f32 = 1;
+  g.nz0 = g.nz1 = 1;
+  g.splitk = P.splitk;
+  g.atomic = P.splitk > 1;
+  g.beta = 1.f;
+  g.rowsum = P.rowsum;
+  const int xy = gx * gy;
+  const dim3 bid(local % gx, (local % xy) / gx, local / xy), grid(gx, gy, gz);
+  gemm_dma_body<WT, 2, 2, true, true, 2, RS, false>(g, P.kchunk, 0, SplitK{nullptr, nullptr}, bid, grid);
 }
 
 // rowsum[row] += sum over splits of part[split][row] (the bias gradient of an atomic split-K dW, fixed order):
@@ -918,6 +980,13 @@ int dma_stages(int wt) {
   return wt == 64 ? s64 : s32;
 }
 
+// ring depth of the weight gradients' (k-major A) 128x128 (wt 64) and 64x64 (wt 32) tiles
+int dw_stages(int wt) {
+  static const int sdw = getenv("DFK_DMA_SDW") ? atoi(getenv("DFK_DMA_SDW")) : 2;
+  static const int sdw32 = getenv("DFK_DMA_SDW32") ? atoi(getenv("DFK_DMA_SDW32")) : 2;   // their 64x64 tiles (A/B)
+  return wt == 64 ? sdw : sdw32;
+}
+
 // wt: 32 -> 64x64 tiles, 64 -> 128x128, 128 -> 256x128 (8 waves)
 void dispatch_dma(const dfk_gemm_args& g, int wt, dim3 grid, int kchunk, int evec, SplitK sk, hipStream_t s) {
   if (g.a.conv_cg > 0 || g.b.conv_cg > 0) {
@@ -927,9 +996,7 @@ void dispatch_dma(const dfk_gemm_args& g, int wt, dim3 grid, int kchunk, int eve
   }
   // weight gradients (k-major A: the token dimension is the reduction) on 128x128 tiles: tuning knob for their ring
   // depth (3 stages measured slower: dW 116 -> 119 us, C2 256.8 -> 247.7 clips/s, profiles/gemm/r4sdw_*)
-  static const int sdw = getenv("DFK_DMA_SDW") ? atoi(getenv("DFK_DMA_SDW")) : 2;
-  static const int sdw32 = getenv("DFK_DMA_SDW32") ? atoi(getenv("DFK_DMA_SDW32")) : 2;   // their 64x64 tiles (A/B)
-  const int st = g.a_kmajor && wt == 64 ? sdw : (g.a_kmajor && wt == 32 ? sdw32 : dma_stages(wt));
+  const int st = g.a_kmajor && (wt == 64 || wt == 32) ? dw_stages(wt) : dma_stages(wt);
   static const int s8w = getenv("DFK_DMA_S8W") ? atoi(getenv("DFK_DMA_S8W")) : 2;   // A/B: ring depth of the 8-wave tiles
   if (wt == 33) {   // 128 x 64 (8 waves of 32 x 32)
     if (s8w == 3) dispatch_dma_s<32, 4, 2, 3>(g, grid, kchunk, evec, sk, s);
@@ -1386,6 +1453,98 @@ uint32_t* dfk_ticket_slice(long n, hipStream_t s) {
 extern "C" int dfk_gemm(const dfk_gemm_args* g, hipStream_t s) {
   if (!g || g->mx_q) return DFK_EINVAL;   // the MX copy of C is a dfk_gemm_mx epilogue
   return g->dtype == DFK_BF16 ? launch<bf16raw>(*g, s) : launch<float>(*g, s);
+}
+
+// The weight-gradient problem g as a record of the grouped launch: true when dfk_gemm would run g as exactly one
+// launch of the 4-wave, 2-stage, k-major / k-major LDS-DMA kernel (no slab split, no bias-gradient partials);
+// the record then holds the tile shape (wt), split and k chunk launch() gives it.
+bool dw_group_plan(const dfk_gemm_args& g, DwProblem& r, int& wt) {
+  if (g.dtype != DFK_BF16 || !g.a_kmajor || !g.b_kmajor || !g.c_f32 || g.mx_q) return false;
+  if (!g.a.ptr || !g.b.ptr || !g.c || g.M <= 0 || g.N <= 0 || g.K <= 0) return false;
+  if (g.nz0 != 1 || g.nz1 != 1 || g.a.conv_cg > 0 || g.b.conv_cg > 0) return false;
+  if (g.bias || g.residual || g.aux || g.act || g.drop.mode || (g.alpha != 0.f && g.alpha != 1.f)) return false;
+  if (g.splitk < 1 || (g.atomic != 0) != (g.splitk > 1) || (!g.atomic && g.beta != 1.f)) return false;
+  if (g.rowsum && g.splitk >= kRsPartialMin) return false;   // partials + rowsum_reduce_kernel: launched singly
+  if (g.K >= 16384) return false;                            // dfk_wgrad_try's range
+  if (!dma_ok(g) || !view_vec(g.a, 8) || !view_vec(g.b, 8) || g.M % 8 || g.N % 8) return false;
+  if (g.a.ld > 0x7fffffffL || g.b.ld > 0x7fffffffL || g.ldc > 0x7fffffffL) return false;
+  // (the tile-shape tuning knobs of launch() that can move a dW off the 4-wave tiles: such runs launch singly)
+  if (auto_splitk<bf16raw>(g) != 1 || getenv("DFK_GEMM_T256") || getenv("DFK_GEMM_T32X")) return false;
+  wt = pick_wt(g);
+  if ((wt != 32 && wt != 64) || dw_stages(wt) != 2) return false;
+  const long gx = dfk_cdiv(g.N, 2 * wt), gy = dfk_cdiv(g.M, 2 * wt);
+  if (gy > 65535 || g.splitk > 65535 || gx * gy * g.splitk > (1L << 24)) return false;
+  r.a = g.a.ptr;
+  r.b = g.b.ptr;
+  r.c = reinterpret_cast<float*>(g.c);
+  r.rowsum = g.rowsum;
+  r.M = g.M, r.N = g.N, r.K = g.K;
+  r.lda = (int32_t)g.a.ld, r.ldb = (int32_t)g.b.ld, r.ldc = (int32_t)g.ldc;
+  r.splitk = g.splitk;
+  r.kchunk = dfk_cdiv(dfk_cdiv(g.K, g.splitk), 64) * 64;
+  r.gx = (int32_t)gx, r.gy = (int32_t)gy;
+  return true;
+}
+
+// byte ranges [p, p + n) overlap
+static bool ranges_meet(const void* p, long n, const void* q, long m) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return p && q && a < b + (uintptr_t)m && b < a + (uintptr_t)n;
+}
+
+extern "C" int dfk_gemm_dw_group(const dfk_gemm_args* problems, int32_t n, hipStream_t s) {
+  if (n < 0 || (n > 0 && !problems)) return DFK_EINVAL;
+  // one open chunk per instantiation: (64x64 | 128x128 tiles) x (with | without the fused bias gradient)
+  DwGroup T[4] = {};
+  int32_t first[4] = {0, 0, 0, 0};   // a chunk's first problem: a chunk of one goes through dfk_gemm
+  auto flush = [&](int k) -> int {
+    DwGroup& G = T[k];
+    const int m = G.n;
+    if (m == 0) return 0;
+    if (m == 1) {
+      G.n = 0;
+      return dfk_gemm(&problems[first[k]], s);
+    }
+    const dim3 grid((unsigned)G.prefix[m]), blk(256);
+    if (k == 0) hipLaunchKernelGGL((gemm_dw_group_kernel<32, false>), grid, blk, 0, s, G);
+    else if (k == 1) hipLaunchKernelGGL((gemm_dw_group_kernel<32, true>), grid, blk, 0, s, G);
+    else if (k == 2) hipLaunchKernelGGL((gemm_dw_group_kernel<64, false>), grid, blk, 0, s, G);
+    else hipLaunchKernelGGL((gemm_dw_group_kernel<64, true>), grid, blk, 0, s, G);
+    G.n = 0;
+    DFK_CHECK_LAUNCH();
+    return 0;
+  };
+  for (int i = 0; i < n; ++i) {
+    const dfk_gemm_args& g = problems[i];
+    DwProblem r;
+    int wt = 0;
+    if (n == 1 || !dw_group_plan(g, r, wt)) {
+      // outputs shared with an open chunk keep their order on the stream
+      for (int k = 0; k < 4; ++k)
+        if (const int rc = flush(k)) return rc;
+      if (const int rc = dfk_gemm(&g, s)) return rc;
+      continue;
+    }
+    const int k = (wt == 64 ? 2 : 0) + (r.rowsum ? 1 : 0);
+    DwGroup& G = T[k];
+    // two problems of one launch must not add into the same dW / db (unsplit problems add without atomics)
+    const long cb = ((long)(r.M - 1) * r.ldc + r.N) * 4, rb = (long)r.M * 4;
+    bool clash = false;
+    for (int j = 0; j < G.n; ++j) {
+      const DwProblem& o = G.p[j];
+      clash = clash || ranges_meet(r.c, cb, o.c, ((long)(o.M - 1) * o.ldc + o.N) * 4) ||
+              ranges_meet(r.rowsum, rb, o.rowsum, (long)o.M * 4);
+    }
+    if (clash || G.n == kDwGroupMax)
+      if (const int rc = flush(k)) return rc;
+    if (G.n == 0) { first[k] = i; G.prefix[0] = 0; }
+    G.p[G.n] = r;
+    G.prefix[G.n + 1] = G.prefix[G.n] + (r.gx * r.gy * r.splitk + 7) / 8 * 8;
+    ++G.n;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (const int rc = flush(k)) return rc;
+  return 0;
 }
 
 extern "C" int64_t dfk_gemm_workspace(const dfk_gemm_args* g) {

@@ -80,6 +80,31 @@ def grad_done(p, g):
     return None
 
 
+def linear_dw_params(dy, x, weight, bias=None, dw=None, db=None, params=None):
+    """The weight (+ bias) gradient of one Linear inside a backward: dW += dy^T x into weight's sink (dw: the flat
+    gradient view of a parameter group) and db += colsum(dy) into bias's (db).  With a ParamStore (direct
+    gradients) a small problem is queued (kernels.linear_dw defer) and its parameters are reported ready when the
+    queue is flushed: by the block's first Linear (GroupLinearFn.backward), at 8 pending problems, by the next
+    weight gradient that launches at once, or at the end of the backward pass at the latest (an engine callback),
+    each on the stream the launches would have used.
+    Returns the (dw, db) values for autograd."""
+    ps = params if params is not None else [p for p in (weight, bias) if p is not None]
+    if dw is None:
+        dw = grad_sink(weight)
+        db = grad_sink(bias) if bias is not None else None
+    if all(_store(p) is not None for p in ps):
+        def done():
+            for p in ps:
+                grad_done(p, None)
+        if K.linear_dw(dy, x, dw, db=db, defer=True, done=done) is True and K.dw_pending() == 1:
+            # the first pending problem: whatever is still queued when this backward pass ends is issued then (a
+            # no-op if a block flush came first; a pass that queues again registers again)
+            torch.autograd.Variable._execution_engine.queue_callback(K.dw_flush_all)
+        return None, None
+    K.linear_dw(dy, x, dw, db=db)
+    return grad_done(weight, dw), (grad_done(bias, db) if bias is not None else None)
+
+
 def checkpoint(fn, *args):
     """torch.utils.checkpoint (non-reentrant) of a region of HIP ops — the reference's use_checkpoint
     (video_swin_transformer.py:267-276, swin_transformer2d.py:428-429): the region's activations are dropped
@@ -151,13 +176,10 @@ class LinearFn(torch.autograd.Function):
                 dx = K.linear_dx(dz, compute_weight(weight, x.dtype))
         dw = db = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1]:
-            db = grad_sink(bias) if want_b else None      # bias gradient fused into the dW pass
-            dw = grad_done(weight, K.linear_dw(dz, x, grad_sink(weight), db=db))
+        if ctx.needs_input_grad[1]:                       # bias gradient fused into the dW pass
+            dw, db = linear_dw_params(dz, x, weight, bias if want_b else None)
         elif want_b:
-            db = K.colsum(dz, grad_sink(bias))
-        if want_b:
-            db = grad_done(bias, db)
+            db = grad_done(bias, K.colsum(dz, grad_sink(bias)))
         return dx, dw, db, None, (dy if ctx.has_res else None), None, None
 
 
@@ -203,9 +225,10 @@ class GroupLinearFn(torch.autograd.Function):
         if any(p.grad is None for p in params):
             st.rebind_grads()
         db = st.grad[bspan[0]:bspan[0] + bspan[1]] if bspan is not None else None
-        K.linear_dw(dy, x, st.grad[wo:wo + wn].view(wshape), db=db)
-        for p in params:
-            grad_done(p, None)
+        linear_dw_params(dy, x, None, dw=st.grad[wo:wo + wn].view(wshape), db=db, params=[_orig(p) for p in params])
+        # the block's first Linear (SwinV2 / wav2vec2 qkv): its backward is the block's last, and the block's queued
+        # weight gradients go out here as one group
+        K.dw_flush()
         return (dx, None, None, None, None, None) + (None,) * len(params)
 
 
@@ -293,12 +316,8 @@ class MlpFn(torch.autograd.Function):
         else:
             dpre = K.linear_dx(dy, compute_weight(w2, dt), act=2, aux=pre, drop=ctx.drop_act)   # (dy W2).Z * gelu'(pre)
             dx = K.linear_dx(dpre, compute_weight(w1, dt), residual=extra) if ctx.needs_input_grad[0] else None
-        db2 = grad_sink(b2)
-        dw2 = grad_done(w2, K.linear_dw(dy, h, grad_sink(w2), db=db2))
-        db2 = grad_done(b2, db2)
-        db1 = grad_sink(b1)
-        dw1 = grad_done(w1, K.linear_dw(dpre, x, grad_sink(w1), db=db1))
-        db1 = grad_done(b1, db1)
+        dw2, db2 = linear_dw_params(dy, h, w2, b2)
+        dw1, db1 = linear_dw_params(dpre, x, w1, b1)
         dres = dyr if (ctx.has_res and not ctx.res_is_input) else None
         return dx, dw1, db1, dw2, db2, dres, None, None, None, None, None
 

@@ -34,6 +34,17 @@ def gemm(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, *, dtype, c_f32=
          rowsum=None, drop=None, alpha=0.0):
     """Raw dfk_gemm.  a/b/c are tensors (base pointers); see include/dfk.h.  drop: rng.Drop spec of the
     output's dropout / DropPath (applied before the residual add)."""
+    _gemm_launch(_gemm_args(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, dtype=dtype, c_f32=c_f32, bias=bias,
+                            residual=residual, ldr=ldr, aux=aux, ldaux=ldaux, act=act, beta=beta, atomic=atomic,
+                            splitk=splitk, nz=nz, a_bs=a_bs, b_bs=b_bs, c_bs=c_bs, r_bs=r_bs, a_conv=a_conv,
+                            b_conv=b_conv, bias_bs1=bias_bs1, rowsum=rowsum, drop=drop, alpha=alpha), c)
+
+
+def _gemm_args(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, *, dtype, c_f32=False, bias=None,
+               residual=None, ldr=0, aux=None, ldaux=0, act=0, beta=0.0, atomic=False, splitk=1,
+               nz=(1, 1), a_bs=(0, 0), b_bs=(0, 0), c_bs=(0, 0), r_bs=(0, 0), a_conv=None, b_conv=None, bias_bs1=0,
+               rowsum=None, drop=None, alpha=0.0):
+    """The dfk_gemm_args of gemm()'s arguments (no workspace yet)."""
     g = L.GemmArgs()
     if drop is not None:
         g.drop = L.drop(drop, c.device)
@@ -61,12 +72,16 @@ def gemm(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, *, dtype, c_f32=
     for t in (a, b, c):
         if not t.is_cuda:
             raise RuntimeError("deepfake_amd: tensors must be on the HIP device (no CPU fallback)")
+    return g
+
+
+def _gemm_launch(g, c):
     ws = None
     nbytes = L.lib().dfk_gemm_workspace(g)
     if nbytes > 0:
         ws = torch.empty(nbytes // 4, device=c.device, dtype=torch.float32)
         g.ws = ws.data_ptr()
-    L.check(L.lib().dfk_gemm(g, L.stream()), f"gemm M={M} N={N} K={K}")
+    L.check(L.lib().dfk_gemm(g, L.stream()), f"gemm M={g.M} N={g.N} K={g.K}")
 
 
 def linear(x, w, b=None, act=0, aux=None, residual=None, out=None, beta=0.0, drop=None):
@@ -194,27 +209,118 @@ def splitk_for(tiles, K, min_k=None):
     return max(1, min(_CU_TARGET_BLOCKS // max(tiles, 1), max(K // min_k, 1)))
 
 
-def linear_dw(dy, x, dw, db=None):
+# Grouped weight gradients (dfk_gemm_dw_group): the small dW problems of one block are queued per stream and issued
+# as one launch per tile shape at dw_flush().  DFK_DW_GROUP=0 / dw_group_policy(0): every problem launches at once.
+_DW_GROUP = [int(os.environ.get("DFK_DW_GROUP", "1"))]
+_DW_GROUP_MAX = 8                       # pending problems at which a queue flushes itself (one native chunk)
+_DW_GROUP_BLOCKS = 768                  # a problem is deferred when its own grid is below 3 workgroups per CU ...
+_DW_GROUP_BYTES = 32 << 20              # ... and its operands (dy and x) take at most this many bytes
+_dw_queues = {}                         # stream handle -> (stream, [(dfk_gemm_args, tensors kept alive, done)])
+
+
+def dw_group_policy(n):
+    """n = 0: weight gradients launch one by one (the A/B baseline); otherwise deferrable ones are grouped.
+    Pending problems are issued first.  Returns the previous setting."""
+    dw_flush_all()
+    old, _DW_GROUP[0] = _DW_GROUP[0], int(n)
+    return old
+
+
+def dw_pending():
+    """Queued weight-gradient problems over all streams."""
+    return sum(len(q) for _, q in _dw_queues.values())
+
+
+def dw_flush():
+    """Issue the current stream's queued weight gradients (one grouped launch per tile shape, in chunks of 8), then
+    run their `done` callbacks (the parameters' grad_ready reports) in queue order."""
+    ent = _dw_queues.pop(torch.cuda.current_stream().cuda_stream, None)
+    if not ent or not ent[1]:
+        return
+    q = ent[1]
+    arr = (L.GemmArgs * len(q))(*[e[0] for e in q])
+    L.check(L.lib().dfk_gemm_dw_group(arr, len(q), L.stream()), f"gemm_dw_group n={len(q)}")
+    for _, _, done in q:
+        if done is not None:
+            done()
+
+
+def dw_flush_all():
+    """dw_flush() of every stream's queue, each on its own stream."""
+    for key in list(_dw_queues):
+        ent = _dw_queues.get(key)
+        if ent is not None:
+            with torch.cuda.stream(ent[0]):
+                dw_flush()
+
+
+def linear_dw_group(problems):
+    """linear_dw of every (dy, x, dw, db) of `problems` (independent: no two share a dw or db) through one
+    dfk_gemm_dw_group call on the current stream: one launch per tile shape and chunk of 8 for the problems that
+    qualify, single launches for the rest."""
+    gs, keep = [], []
+    for dy, x, dw, db in problems:
+        g, _ = _dw_args(dy, x, dw, db)
+        nbytes = L.lib().dfk_gemm_workspace(g)
+        if nbytes > 0:   # a problem the native side launches singly, with its workspace
+            keep.append(torch.empty(nbytes // 4, device=dw.device, dtype=torch.float32))
+            g.ws = keep[-1].data_ptr()
+        gs.append(g)
+    if gs:
+        arr = (L.GemmArgs * len(gs))(*gs)
+        L.check(L.lib().dfk_gemm_dw_group(arr, len(gs), L.stream()), f"gemm_dw_group n={len(gs)}")
+
+
+def linear_dw(dy, x, dw, db=None, defer=False, done=None):
     """dw[N,K] (fp32, +=) += dy[M,N]^T @ x[M,K]; with db [N] fp32: db += column sums of dy (the bias
     gradient) from the same pass over dy.  Output grids that fill the chip run unsplit and add in the
-    epilogue; skinny ones split the M reduction and add fp32 partials atomically."""
+    epilogue; skinny ones split the M reduction and add fp32 partials atomically.
+    defer: a small problem is queued on the current stream instead (it holds dy, x, dw and db until dw_flush(),
+    which launches the queue as a group and then calls done()); any other problem launches now, then calls done().
+    Returns True when the problem was queued, else dw."""
+    g, blocks = _dw_args(dy, x, dw, db)
+    M, N = dy.shape
+    K = x.shape[1]
+    if (defer and _DW_GROUP[0] and blocks < _DW_GROUP_BLOCKS and M * (N + K) * 2 <= _DW_GROUP_BYTES
+            and dy.dtype == torch.bfloat16 and L.lib().dfk_gemm_workspace(g) == 0):
+        cur = torch.cuda.current_stream()
+        q = _dw_queues.setdefault(cur.cuda_stream, (cur, []))[1]
+        q.append((g, (dy, x, dw, db), done))
+        if len(q) >= _DW_GROUP_MAX:
+            dw_flush()
+        return True
+    if _dw_queues:
+        # a weight gradient that launches now takes the stream's pending ones with it: a problem queued outside a
+        # block (wav2vec2's feature projection) would otherwise wait for the end of the backward pass and run
+        # after the trunk's last kernel, on the step's critical tail
+        dw_flush()
+    _gemm_launch(g, dw)
+    if done is not None:
+        done()
+    return dw
+
+
+def _dw_args(dy, x, dw, db):
+    """(dfk_gemm_args, workgroups) of linear_dw's problem: the split plan of the weight-gradient GEMM."""
     M, N = dy.shape
     K = x.shape[1]
     if math.ceil(N / 64) * math.ceil(K / 64) >= _DW_UNSPLIT64:
-        gemm(dy, dy.stride(0), True, x, x.stride(0), True, N, K, M, dw, dw.stride(0), dtype=L.dt(dy), c_f32=True,
-             beta=1.0, rowsum=db)
-        return dw
-    tiles = math.ceil(N / 128) * math.ceil(K / 128)
-    s = splitk_for(tiles, M)
-    # fp32 partial bytes (splits x N x K x 4) kept to a quarter of the operand bytes read, except that small
-    # grids keep up to 8 splits for parallelism (C2 sweep: mel1.fc1 [25088]x512x128 98 -> 30 splits, 42 -> 28 us)
-    s = max(1, min(s, max(8, M * (N + K) // (8 * N * K))))
-    if _DW_XCD and tiles > 1 and s >= 16:
-        s -= s % 8   # a multiple of 8 splits: the kernel puts each split's tiles on one XCD (shared operand in L2)
-    slab = s > 1 and _DW_SLAB   # A/B: fp32 split slabs + one reduce pass instead of the splits' fp32 atomics
-    gemm(dy, dy.stride(0), True, x, x.stride(0), True, N, K, M, dw, dw.stride(0), dtype=L.dt(dy), c_f32=True,
-         atomic=s > 1 and not slab, beta=1.0, splitk=s, rowsum=db)
-    return dw
+        blocks = math.ceil(N / 64) * math.ceil(K / 64)
+        g = _gemm_args(dy, dy.stride(0), True, x, x.stride(0), True, N, K, M, dw, dw.stride(0), dtype=L.dt(dy),
+                       c_f32=True, beta=1.0, rowsum=db)
+    else:
+        tiles = math.ceil(N / 128) * math.ceil(K / 128)
+        s = splitk_for(tiles, M)
+        # fp32 partial bytes (splits x N x K x 4) kept to a quarter of the operand bytes read, except that small
+        # grids keep up to 8 splits for parallelism (C2 sweep: mel1.fc1 [25088]x512x128 98 -> 30 splits, 42 -> 28 us)
+        s = max(1, min(s, max(8, M * (N + K) // (8 * N * K))))
+        if _DW_XCD and tiles > 1 and s >= 16:
+            s -= s % 8   # a multiple of 8 splits: the kernel puts each split's tiles on one XCD (shared operand in L2)
+        slab = s > 1 and _DW_SLAB   # A/B: fp32 split slabs + one reduce pass instead of the splits' fp32 atomics
+        blocks = tiles * s
+        g = _gemm_args(dy, dy.stride(0), True, x, x.stride(0), True, N, K, M, dw, dw.stride(0), dtype=L.dt(dy),
+                       c_f32=True, atomic=s > 1 and not slab, beta=1.0, splitk=s, rowsum=db)
+    return g, blocks
 
 
 def colsum(x, out):

@@ -26,6 +26,7 @@ import time
 import torch
 import torch.distributed as dist
 
+from . import kernels as K
 from . import rng
 from .ddp import GradBucketer, fr_last_id, recorder_on
 from .optim import CosineAnnealingLR, FusedAdamW, FusedSGD, ParamEMA
@@ -194,6 +195,9 @@ class TrainStep:
         if before_backward is not None:
             before_backward()
         (loss * scale if scale != 1.0 else loss).backward()
+        # deferred weight gradients left in a trunk's queue go out on that trunk's stream before the streams join
+        # (the backward pass's own end-of-pass flush has normally emptied the queues already)
+        K.dw_flush_all()
         if getattr(self.model, "parallel_branches", False):
             self.model.join_branches()
         return loss, prob

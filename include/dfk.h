@@ -110,6 +110,15 @@ int dfk_gemm(const dfk_gemm_args* g, hipStream_t stream);
  * wav2vec2 / SwinV2-stage-3 Linears, M ~ 1.6k rows) are split along K into fp32
  * slabs that a second kernel sums before the epilogue.  0 = no split. */
 int64_t dfk_gemm_workspace(const dfk_gemm_args* g);
+/* n independent weight-gradient GEMMs (dW += dy^T x of the Linears of one block: nothing reads them before the
+ * optimizer) in as few launches as possible.  A problem qualifies when dfk_gemm would run it as one launch of the
+ * bf16 LDS-DMA kernel with both operands k-major and fp32 C: beta = 1 unsplit, or atomic = 1 with splitk > 1
+ * (below the 32 splits from which the bias gradient goes through partials), optional rowsum, no other epilogue,
+ * no workspace.  Qualifying problems are bucketed by tile shape and rowsum and run in chunks of up to 8 per
+ * launch; each keeps the tile shape, split count, k order and tile order it has under dfk_gemm, so its sums are
+ * those of dfk_gemm.  Problems of one chunk never share an output range (such a problem starts a new chunk).
+ * Every other problem, and a chunk of one, goes through dfk_gemm unchanged (with its own ws). */
+int dfk_gemm_dw_group(const dfk_gemm_args* problems, int32_t n, hipStream_t stream);
 
 /* ---- MX-fp8 (OCP microscaling) GEMM path of the C4 Swin-B video trunk (BASELINE configs[3]: "fp8 MFMA
  * attention/QKV path"): the qkv / proj / fc1 / fc2 Linears of video_swin_transformer.py:134-136 (WindowAttention3D)

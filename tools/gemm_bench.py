@@ -44,12 +44,39 @@ def t(fn, it=10):
     return s.elapsed_time(e) / it / 1e3
 
 
+DW_GROUPS = {  # the four weight gradients of one block (name prefix in SHAPES; qkv of mel3 is not listed there)
+    "mel3": [(1568, 1536, 512), (1568, 512, 512), (1568, 2048, 512), (1568, 512, 2048)],
+    "w2v": [(1592, 2304, 768), (1592, 768, 768), (1592, 3072, 768), (1592, 768, 3072)],
+}
+
+
+def dw_groups():
+    """The dW + db problems of one SwinV2 stage-3 block / one wav2vec2 layer: four single launches against one
+    dfk_gemm_dw_group call (kernels.linear_dw_group), per-block time of 10 blocks replayed from one graph."""
+    for name, shapes in DW_GROUPS.items():
+        probs = []
+        for M, N, Kd in shapes:
+            probs.append((torch.randn(M, N, device="cuda").bfloat16(), torch.randn(M, Kd, device="cuda").bfloat16(),
+                          torch.zeros(N, Kd, device="cuda"), torch.zeros(N, device="cuda")))
+
+        def singles():
+            for p in probs:
+                K.linear_dw(*p)
+        ts, tg = t(singles), t(lambda: K.linear_dw_group(probs))
+        each = [t(lambda p=p: K.linear_dw(*p)) for p in probs]
+        print(f"{name:5s} dW+db of one block: 4 singles {ts * 1e6:6.1f} us, grouped {tg * 1e6:6.1f} us  "
+              f"(each alone: {' / '.join(f'{v * 1e6:.1f}' for v in each)} us)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--dw-group", action="store_true", help="only time the grouped weight gradients of one block")
     ap.add_argument("--torch", action="store_true", help="also time torch (hipBLASLt) for reference")
     ap.add_argument("--only", default="", help="comma-separated shape-name prefixes")
     a = ap.parse_args()
+    if a.dw_group:
+        return dw_groups()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     tot = {"fwd": 0.0, "dx": 0.0, "dw": 0.0}
     for name, M, N, Kd in SHAPES:
