@@ -10,13 +10,20 @@
 
 namespace {
 
+// channels per thread of im2col2d: 8 (16-byte vectors) when every 8-channel group of x and out is 16-byte
+// aligned, else 1.  A channel slice of a wider buffer can start off that alignment even with C and ldx
+// multiples of 8, so the base pointers count too.  The host decides once and hands the kernel its choice.
+int im2col2d_vec(const void* x, long ldx, const void* out, int C) {
+  const bool aligned = (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
+  return (C % 8 == 0 && ldx % 8 == 0 && aligned) ? 8 : 1;
+}
+
 // out[(n*Ho + oh)*Wo + ow][(ky*kw + kx)*C + c] = x[n, oh*sh - ph + ky, ow*sw - pw + kx, c]  (0 outside)
 template <typename T>
 __global__ __launch_bounds__(256) void im2col2d_kernel(const T* __restrict__ x, long ldx, T* __restrict__ out,
                                                        int N, int H, int W, int C, int kh, int kw, int sh, int sw,
-                                                       int ph, int pw, int Ho, int Wo) {
+                                                       int ph, int pw, int Ho, int Wo, int VEC) {
   const long cols = (long)kh * kw * C;
-  const int VEC = (C % 8 == 0 && ldx % 8 == 0) ? 8 : 1;
   const long per_row = cols / VEC;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)N * Ho * Wo * per_row) return;
@@ -246,12 +253,12 @@ long rows_per_block(long rows) { return rows < 256 ? rows : std::max<long>(64, r
 extern "C" int dfk_im2col2d(const void* x, int64_t ldx, void* out, const dfk_conv2d_geo* g, int dtype, hipStream_t s) {
   if (!x || !out || !g || g->C <= 0 || g->kh <= 0 || g->kw <= 0 || g->sh <= 0 || g->sw <= 0) return DFK_EINVAL;
   const long cols = (long)g->kh * g->kw * g->C;
-  const int vec = (g->C % 8 == 0 && ldx % 8 == 0) ? 8 : 1;
+  const int vec = im2col2d_vec(x, ldx, out, g->C);
   const long n = (long)g->N * g->Ho * g->Wo * (cols / vec);
   if (n <= 0) return 0;
   const dim3 grid((unsigned)dfk_cdiv(n, 256));
 #define IM2COL(T) hipLaunchKernelGGL(im2col2d_kernel<T>, grid, dim3(256), 0, s, (const T*)x, (long)ldx, (T*)out, g->N, \
-                                     g->H, g->W, g->C, g->kh, g->kw, g->sh, g->sw, g->ph, g->pw, g->Ho, g->Wo)
+                                     g->H, g->W, g->C, g->kh, g->kw, g->sh, g->sw, g->ph, g->pw, g->Ho, g->Wo, vec)
   if (dtype == DFK_BF16) IM2COL(bf16raw); else IM2COL(float);
 #undef IM2COL
   DFK_CHECK_LAUNCH();
@@ -354,7 +361,8 @@ extern "C" int dfk_pool2d_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, 
 
 extern "C" int dfk_pool2d_bwd(const void* x, int64_t ldx, const void* dy, int64_t lddy, void* dx, int64_t lddx,
                               const dfk_conv2d_geo* g, int mode, int accumulate, int dtype, hipStream_t s) {
-  if (!x || !dy || !dx || !g || g->C <= 0 || g->kh != g->kw || g->sh != g->sw || g->ph != g->pw) return DFK_EINVAL;
+  if (!x || !dy || !dx || !g || g->C <= 0 || g->kh != g->kw || g->sh != g->sw || g->ph != g->pw || (mode != 0 && mode != 1))
+    return DFK_EINVAL;
   const long n = (long)g->N * g->H * g->W * g->C;
   if (n <= 0) return 0;
   const dim3 grid((unsigned)dfk_cdiv(n, 256));

@@ -936,7 +936,7 @@ class ConvBNReLUFn(torch.autograd.Function):
         for i, q in ((1, weight), (2, gamma), (3, beta)):
             grad_use(ctx, i, q)
         ctx.save_for_backward(cols, w2, z, y, mean, rstd, weight, gamma, beta)
-        ctx.g, ctx.one, ctx.xshape = g, one, x.shape
+        ctx.g, ctx.one, ctx.xshape, ctx.training = g, one, x.shape, training
         return y.view(N, g.Ho, g.Wo, Cout)
 
     @staticmethod
@@ -944,9 +944,15 @@ class ConvBNReLUFn(torch.autograd.Function):
         cols, w2, z, y, mean, rstd, weight, gamma, beta = ctx.saved_tensors
         g = ctx.g
         dy2 = dy.reshape(z.shape).contiguous()
-        dz = torch.empty_like(z)
         dg, db = grad_sink(gamma), grad_sink(beta)
-        K.bn2d_bwd(dy2, y, z, dz, mean, rstd, gamma.detach().float(), True, dg, db)
+        if ctx.training:
+            dz = torch.empty_like(z)
+            K.bn2d_bwd(dy2, y, z, dz, mean, rstd, gamma.detach().float(), True, dg, db)
+        else:   # fixed statistics: no gradient flows through mean / rstd (a cold path, so a few torch ops)
+            d = dy2.float() * (y > 0)
+            dg += (d * ((z.float() - mean) * rstd)).sum(0)
+            db += d.sum(0)
+            dz = (d * (gamma.detach().float() * rstd)).to(z.dtype)
         dw = grad_sink(weight)
         kh, kw = g.kh, g.kw
         if kh == 1 and kw == 1:

@@ -621,7 +621,8 @@ typedef struct {
 } dfk_conv2d_geo;
 /* im2col of nn.Conv2d (InceptionResV2.py:9): out [N*Ho*Wo][(ky*kw + kx)*C + c] (zero padding); the conv is
  * then the GEMM out . W'^T with W' = weight.permute(0,2,3,1) [Cout][kh*kw*C].  col2im2d: the input gradient
- * dx (=, or += when accumulate) from dcols of the same layout (a gather: no atomics). */
+ * dx (=, or += when accumulate) from dcols of the same layout (a gather: no atomics).  x / dx may start at any
+ * channel of a wider buffer: im2col2d moves 16-byte vectors only when C, ldx and both base pointers allow it. */
 int dfk_im2col2d(const void* x, int64_t ldx, void* out, const dfk_conv2d_geo* g, int dtype, hipStream_t stream);
 int dfk_col2im2d(const void* dcols, void* dx, int64_t ldx, const dfk_conv2d_geo* g, int accumulate, int dtype,
                  hipStream_t stream);
