@@ -786,19 +786,16 @@ __global__ __launch_bounds__(256) void wattn_tab3_kernel(const dfk_wattn_args a,
   }
 }
 
-// identity operands of the bias product (B[slot][n] = slot == n - 16c), and the row-sum selector: a
-// v_mfma_f32_16x16x32_bf16 A operand (lane l: row l & 15, k = 8 (l >> 4) + j) that is 1 iff row == (l >> 4) & 1,
-// so that with a 32x32x16 B fragment X (query l & 31 on the lane) the 16x16 product's row 0 / row 1 hold the
-// column sums of X for queries 0-15 / 16-31 — in lanes 0-15, registers 0 / 1 (4 accumulator registers, not 16)
-__device__ __forceinline__ void bias_ident(int lane, bf16x8& i0, bf16x8& i1, bf16x8& sel) {
-  const int r = lane & 31, hh = lane >> 5;
+// the row-sum selector: a v_mfma_f32_16x16x32_bf16 A operand (lane l: row l & 15, k = 8 (l >> 4) + j) that is 1 iff
+// row == (l >> 4) & 1, so that with a 32x32x16 B fragment X (query l & 31 on the lane) the 16x16 product's row 0 /
+// row 1 hold the column sums of X for queries 0-15 / 16-31 — in lanes 0-15, registers 0 / 1 (4 accumulator
+// registers, not 16)
+__device__ __forceinline__ bf16x8 rowsum_sel(int lane) {
   const float sv = (lane & 15) == ((lane >> 4) & 1) ? 1.f : 0.f;
+  bf16x8 sel;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    i0[j] = (__bf16)(8 * hh + j == r ? 1.f : 0.f);
-    i1[j] = (__bf16)(8 * hh + j + 16 == r ? 1.f : 0.f);
-    sel[j] = (__bf16)sv;
-  }
+  for (int j = 0; j < 8; ++j) sel[j] = (__bf16)sv;
+  return sel;
 }
 
 // the row sum of query r (= lane & 31) from the selector accumulator: lane r & 15, register r >> 4
@@ -821,17 +818,18 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// Forward v3.  One workgroup = one (clip, window, head) (x qsplit), 4 waves; K and V of the window staged once
-// in XOR-swizzled LDS tiles.  Per wave and 32-query block, per 32-key block:
-//   D = K Q'^T + bias' - m        (Q' = Q * scale * log2e; -m enters as the C input of the first MFMA: a
-//                                  16-register tile held per lane, rewritten only on a rescale)
+// Forward v3 (no score bias at all: wav2vec2; the bias-table forms are v4 and v6).  One workgroup = one (clip,
+// window, head) (x qsplit), 4 waves; K and V of the window staged once in XOR-swizzled LDS tiles.  Per wave and
+// 32-query block, per 32-key block:
+//   D = K Q'^T - m                (Q' = Q * scale * log2e; -m enters as one more MFMA k-step, keys beyond N are
+//                                  set to -inf in the last block)
 //   P = 2^D                        (one v_exp per score, no subtract, no multiply)
 //   O^T += V^T P^T, l = ones^T P^T (both on the MFMA; P^T is the accumulator tile converted in place)
 // with a lazy rescale (m moves only when a block's max exceeds it by kRescale, or on the first block).
 // Lane l holds query 32 qb + (l & 31) and keys (j & 3) + 8 (j >> 2) + 4 (l >> 5) of every tile.
-template <int HD, bool TAB, bool DROP>
+template <int HD, bool DROP>
 __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_kernel(const dfk_wattn_args a, const Geo g, int qsplit,
-                                                         const bf16raw* __restrict__ tab) {
+                                                         const bf16raw* __restrict__ /* the table kernels' launch signature */) {
   constexpr int NKK = HD / 16, NOT = HD / 32, CH = HD / 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16raw* Ks = reinterpret_cast<bf16raw*>(smem);
@@ -870,9 +868,7 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
     }
   }
   const int nkb = g.Np / 32, nqb = g.Np / 32;
-  const bf16raw* tch = TAB ? tab + ((long)wu.cls * a.heads + head) * (long)g.Np * g.Np : nullptr;
-  bf16x8 id0, id1, sel;
-  bias_ident(lane, id0, id1, sel);
+  const bf16x8 sel = rowsum_sel(lane);
   const float qs = a.scale * kLog2e;
   const DropCtx dc = drop_ctx(a.drop);
   __syncthreads();
@@ -904,12 +900,6 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
   bf16x8 onesA;
 #pragma unroll
   for (int j = 0; j < 8; ++j) onesA[j] = (__bf16)(hh == 0 && j == 0 ? 1.f : 0.f);
-  // bias tiles through a buffer descriptor: the lane's 16 B in a VGPR offset, the (qb, kb) tile in an SGPR
-  const uint64_t tp64 = reinterpret_cast<uint64_t>(tch);   // wave-uniform: keep the descriptor in SGPRs
-  const uint64_t tpu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(tp64 >> 32)) << 32) |
-                       (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)tp64);   // no sign extension
-  const __amdgpu_buffer_rsrc_t trs =
-      __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(tpu), (short)0, TAB ? 0x7fffffff : 0, 0x00020000);
   load_q(min(wu.qpart * nw + wave, nqb - 1));
   for (int qb = wu.qpart * nw + wave; qb < nqb; qb += qstep) {
     const int qrow = qrown;
@@ -920,14 +910,6 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
       for (int j = 0; j < 8; ++j) qf[kk][j] = (__bf16)((float)qfn[kk][j] * qs);
     }
     load_q(min(qb + qstep, nqb - 1));
-    auto load_bias = [&](bf16x8 (&bt)[2], int kb) {
-      if constexpr (TAB) {
-        const int so = __builtin_amdgcn_readfirstlane((qb * nkb + kb) * 2048);   // bytes: 1024 bf16 per (qb, kb)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-          bt[c] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(trs, lane * 16, so + c * 1024, 0));
-      }
-    };
     f32x16 o[NOT];
     f32x4 l4 = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = 0.f;
@@ -938,8 +920,6 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
     for (int ot = 0; ot < NOT; ++ot)
 #pragma unroll
       for (int j = 0; j < 16; ++j) o[ot][j] = 0.f;
-    bf16x8 bt[2];
-    load_bias(bt, 0);
     auto block = [&](int kb) {
       const bf16raw* kbase = Ks + kb * 32 * HD;
       const bf16raw* vbase = Vs + kb * 32 * HD;
@@ -947,16 +927,10 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
       f32x16 d = mfma32(onesA, mB, f32x16{});
 #pragma unroll
       for (int kk = 0; kk < NKK; ++kk) d = mfma32(*reinterpret_cast<const bf16x8*>(kbase + koff[kk]), qf[kk], d);
-      if constexpr (TAB) {
-        d = mfma32(bt[0], id0, d);
-        d = mfma32(bt[1], id1, d);
-        load_bias(bt, min(kb + 1, nkb - 1));   // next block's tile: in flight under this block's softmax and PV
-      } else {
-        if (kb == nkb - 1) {   // keys beyond N (no table: the only padded key block)
+      if (kb == nkb - 1) {   // keys beyond N (no table: the only padded key block)
 #pragma unroll
-          for (int j = 0; j < 16; ++j)
-            if (kb * 32 + (j & 3) + 8 * (j >> 2) + 4 * hh >= g.N) d[j] = -INFINITY;
-        }
+        for (int j = 0; j < 16; ++j)
+          if (kb * 32 + (j & 3) + 8 * (j >> 2) + 4 * hh >= g.N) d[j] = -INFINITY;
       }
       // lazy rescale: the block max relative to m (lanes l and l^32 hold the same query)
       float x0 = max3f(d[0], d[1], d[2]), x1 = max3f(d[3], d[4], d[5]), x2 = max3f(d[6], d[7], d[8]);
@@ -1659,8 +1633,8 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// Forward v6 (hd 32, bias tables, no dropout; experiment, DFK_WATTN_V=6): v5 on v_mfma_f32_16x16x32_bf16.  With
-// K = hd = 32 one 16x16x32 product is a whole 16x16 score sub-tile: the four sub-tiles of a 32x32 block are four
+// Forward v6 (hd 32, bias tables, no dropout; the default from kV6MinQb query blocks): v5 on
+// v_mfma_f32_16x16x32_bf16.  With K = hd = 32 one 16x16x32 product is a whole 16x16 score sub-tile: the four sub-tiles of a 32x32 block are four
 // independent MFMAs with no accumulate chain, and each sub-tile's v_exp can start as soon as its own product is
 // done (v5's 32x32x16 tile waits on two dependent products before its first v_exp; r5e ablation: that wait is
 // ~50 us of the stage-1 launch).  Lane l holds, per chain and query half qh, query 32 qb + 16 qh + (l & 15) and keys
@@ -1668,12 +1642,7 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
 // (k-slots j <-> key 16 (j >> 2) + 4 (l >> 4) + (j & 3)), and V^T is read with the same slot order by ds_read_tr16.
 // Row statistics are per (chain, half) and reduce over the 4 lane groups.  Bias tables in the fwd16 layout
 // (wattn_tab3_kernel fwd16: [qh][64 lanes][kh][r]).
-// ONES (A/B, non-BAL only): the softmax denominators by a third PV-shaped MFMA with an all-ones A operand (every
-// output row = the column's sum of the bf16 P that also multiplies V) instead of 8 VALU adds per query half and
-// the lane-group sum at the store: -16 VALU adds per 32x32 block for +2 MFMAs on the matrix pipe, which has slack
-// W8 (A/B): up to 8 waves per workgroup (one query-block pair each) instead of 4 looping over the pairs
-template <bool BAL, bool ONES = false, bool W8 = false>
-__global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(const dfk_wattn_args a, const Geo g, int qsplit,
+__global__ __launch_bounds__(256, 3) void wattn_fwd6_kernel(const dfk_wattn_args a, const Geo g, int qsplit,
                                                            const bf16raw* __restrict__ tab) {
   constexpr int HD = 32, CH = HD / 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1740,6 +1709,8 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
     }
   };
   // element index in a chain's 16 registers: scores d[8 qh + 4 kh + r], output o[8 qh + 4 eh + r]
+  // (every caller passes the key blocks [k0, k1) = [0, nkb); the range arguments and the gather lambda above stay
+  // because folding them moves the register allocation of the measured kernel)
   auto chains = [&](auto nc_t, auto safe_t, const int (&qb)[2], const bf16x8 (&qf)[2][2], int k0, int k1,
                     f32x16 (&o)[2], float (&ls)[2][2], float (&m)[2][2]) __attribute__((always_inline)) {
     constexpr int NC = decltype(nc_t)::value;
@@ -1755,16 +1726,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
     };
     uint4 bt[2][2];
     load_bias(bt, k0);
-    f32x4 lac[2][2];   // ONES: the denominators as MFMA accumulators (all four registers hold the column's sum)
-    bf16x8 ones;
-    if constexpr (ONES) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int qh = 0; qh < 2; ++qh) lac[u][qh] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
     // one key block; KH: the block's second 16 keys are all beyond N (the window's last block when N mod 32 is in
     // (0, 16]: 392 = 12 x 32 + 8): their products, exponentials and P are skipped (P = 0 there anyway)
     auto block = [&](int kb, auto kh_t) __attribute__((always_inline)) {
@@ -1821,7 +1782,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
                 d1[j] -= delta;
               }
               ls[u][qh] *= alpha;
-              if constexpr (ONES) lac[u][qh] = lac[u][qh] * alpha;
 #pragma unroll
               for (int j = 0; j < 8; ++j) o[u][8 * qh + j] *= alpha;
             }
@@ -1832,14 +1792,11 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
             p[j] = __builtin_amdgcn_exp2f(d0[j]);
             p[4 + j] = KH ? 0.f : __builtin_amdgcn_exp2f(d1[j]);
           }
-          if constexpr (!ONES) {
-            if constexpr (KH) ls[u][qh] += (p[0] + p[1]) + (p[2] + p[3]);
-            else ls[u][qh] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-          }
+          if constexpr (KH) ls[u][qh] += (p[0] + p[1]) + (p[2] + p[3]);
+          else ls[u][qh] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
           bf16x8 pv;
 #pragma unroll
           for (int j = 0; j < 8; ++j) pv[j] = (__bf16)p[j];
-          if constexpr (ONES) lac[u][qh] = mfma16(ones, pv, lac[u][qh]);
 #pragma unroll
           for (int eh = 0; eh < 2; ++eh) {
             f32x4 acc = {o[u][8 * qh + 4 * eh], o[u][8 * qh + 4 * eh + 1], o[u][8 * qh + 4 * eh + 2],
@@ -1857,12 +1814,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
     const int kfull = tail_half ? k1 - 1 : k1;
     for (int kb = k0; kb < kfull; ++kb) block(kb, std::false_type{});
     if (tail_half) block(k1 - 1, std::true_type{});
-    if constexpr (ONES) {
-#pragma unroll
-      for (int u = 0; u < NC; ++u)
-#pragma unroll
-        for (int qh = 0; qh < 2; ++qh) ls[u][qh] += lac[u][qh][0];
-    }
   };
   auto zero = [&](f32x16 (&o)[2], float (&ls)[2][2], float (&m)[2][2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -1874,13 +1825,12 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
     }
   };
   // O = O^T / l for block qb (lane: queries 32 qb + 16 qh + ql, channels 16 eh + 4 g16 + 0..3), lse; true: rejected
-  auto store = [&](int qb, const f32x16& o, const float (&ls)[2], const float (&m)[2], bool real = true,
-                   bool reduced = false) __attribute__((always_inline)) -> bool {
-    if (!real) return false;
+  auto store = [&](int qb, const f32x16& o, const float (&ls)[2], const float (&m)[2])
+                   __attribute__((always_inline)) -> bool {
     bool bad = false;
 #pragma unroll
     for (int qh = 0; qh < 2; ++qh) {
-      const float l = reduced ? ls[qh] : grp_sum4(ls[qh]);
+      const float l = grp_sum4(ls[qh]);
       const float inv = 1.f / l;
       const int q = qb * 32 + 16 * qh + ql;
       const int row = q < g.N ? token_info_row(a, g, b, win, q) : -2;
@@ -1911,7 +1861,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
     float ls[2][2], m[2][2];
     zero(o, ls, m);
     chains(I1{}, SAFE{}, qbs, qf, 0, nkb, o, ls, m);
-    store(qb, o[0], ls[0], m[0], true, ONES);
+    store(qb, o[0], ls[0], m[0]);
   };
   auto full = [&](int qb0, int qb1) __attribute__((always_inline)) {
     const int qb[2] = {qb0, min(qb1, nqb - 1)};
@@ -1924,128 +1874,19 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 3) void wattn_fwd6_kernel(
     if (qb1 < nqb) {
       load_q(qb[1], qf[1]);
       chains(I2{}, FAST{}, qb, qf, 0, nkb, o, ls, m);
-      bad = store(qb[0], o[0], ls[0], m[0], true, ONES);
-      bad |= store(qb[1], o[1], ls[1], m[1], true, ONES);
+      bad = store(qb[0], o[0], ls[0], m[0]);
+      bad |= store(qb[1], o[1], ls[1], m[1]);
     } else {   // an odd block count's last block: one chain (it was computed twice, the copy discarded)
       chains(I1{}, FAST{}, qb, qf, 0, nkb, o, ls, m);
-      bad = store(qb[0], o[0], ls[0], m[0], true, ONES);
+      bad = store(qb[0], o[0], ls[0], m[0]);
     }
     if (__builtin_amdgcn_ballot_w64(bad) != 0) {
       safe_block(qb[0]);
       if (qb1 < nqb) safe_block(qb1);
     }
   };
-  const int nw = dfk_bdim() >> 6;
-  static_assert(!(BAL && ONES), "ONES: the simple schedule only");
-  if constexpr (!BAL) {
-    const int ngrp = (nqb + 1) / 2, qstep = nw * qsplit;
-    for (int gi = wu.qpart * nw + wave; gi < ngrp; gi += qstep) full(2 * gi, 2 * gi + 1);
-    return;
-  } else {
-    // v5's balanced schedule (host guarantees: qsplit == 1, 4 waves, pairs % 4 in {0, 1, 2}); the row sums are
-    // reduced over the lane groups before they go to LDS, so the l's of a wave fit one float4 slot per lane
-    int& f5_flag = *reinterpret_cast<int*>(smem + max(4 * g.Np * HD, 4 * kF5Slots * 1024));
-    if (tid == 0) f5_flag = 0;
-    const int pairs = nqb / 2, tail = nqb & 1, R = pairs % 4, p1 = pairs - R;
-    for (int p = wave; p < p1; p += 4) full(2 * p, 2 * p + 1);
-    f32x16 oa[2], ob[2];
-    float la[2][2], lb[2][2], ma[2][2], mb[2][2];
-    zero(oa, la, ma);
-    zero(ob, lb, mb);
-    const int pa = R == 2 ? p1 + (wave >> 1) : p1;
-    if (R > 0) {
-      const int ka0 = R == 2 ? ((wave & 1) ? (nkb + 1) / 2 : 0) : (wave * nkb) / 4;
-      const int ka1 = R == 2 ? ((wave & 1) ? nkb : (nkb + 1) / 2) : ((wave + 1) * nkb) / 4;
-      const int qb[2] = {2 * pa, 2 * pa + 1};
-      bf16x8 qf[2][2];
-      load_q(qb[0], qf[0]);
-      load_q(qb[1], qf[1]);
-      chains(I2{}, FAST{}, qb, qf, ka0, ka1, oa, la, ma);
-    }
-    if (tail) {
-      const int qb[2] = {nqb - 1, nqb - 1};
-      bf16x8 qf[2][2];
-      load_q(qb[0], qf[0]);
-      chains(I1{}, FAST{}, qb, qf, (wave * nkb) / 4, ((wave + 1) * nkb) / 4, ob, lb, mb);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int qh = 0; qh < 2; ++qh) {
-        la[u][qh] = grp_sum4(la[u][qh]);
-        lb[u][qh] = grp_sum4(lb[u][qh]);
-      }
-    __syncthreads();   // every wave is done with K / V: their space takes the partials
-    float4* ps = reinterpret_cast<float4*>(smem);
-    auto slot = [&](int w, int s) __attribute__((always_inline)) -> float4* { return ps + (w * kF5Slots + s) * 64 + lane; };
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int j4 = 0; j4 < 4; ++j4)
-        *slot(wave, 4 * u + j4) = make_float4(oa[u][4 * j4], oa[u][4 * j4 + 1], oa[u][4 * j4 + 2], oa[u][4 * j4 + 3]);
-#pragma unroll
-    for (int j4 = 0; j4 < 4; ++j4)
-      *slot(wave, 8 + j4) = make_float4(ob[0][4 * j4], ob[0][4 * j4 + 1], ob[0][4 * j4 + 2], ob[0][4 * j4 + 3]);
-    // slot 12: lanes of group 0 hold the pair's (chain, half) sums, group 1 the tail's (query = lane & 15)
-    *slot(wave, 12) = g16 == 0 ? make_float4(la[0][0], la[0][1], la[1][0], la[1][1])
-                               : make_float4(lb[0][0], lb[0][1], 0.f, 0.f);
-    __syncthreads();
-    const bool fin_pair = R == 2 ? (wave == 0 || wave == 2) : (R == 1 && wave == 0);
-    const bool fin_tail = tail && wave == (R == 2 ? 3 : (R == 1 ? 1 : 0));
-    bool bad2 = false;
-    if (fin_pair) {
-      const int w0 = R == 2 ? wave : 0, w1 = R == 2 ? wave + 2 : 4;
-      f32x16 o[2];
-      float ls[2][2], m0[2] = {0.f, 0.f};
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        ls[u][0] = ls[u][1] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[u][j] = 0.f;
-      }
-      for (int w = w0; w < w1; ++w) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int j4 = 0; j4 < 4; ++j4) {
-            const float4 v = *slot(w, 4 * u + j4);
-            o[u][4 * j4] += v.x; o[u][4 * j4 + 1] += v.y; o[u][4 * j4 + 2] += v.z; o[u][4 * j4 + 3] += v.w;
-          }
-        const float4 lv = ps[(w * kF5Slots + 12) * 64 + ql];
-        ls[0][0] += lv.x; ls[0][1] += lv.y; ls[1][0] += lv.z; ls[1][1] += lv.w;
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) bad2 |= store(2 * pa + u, o[u], ls[u], m0, true, true);
-    }
-    if (fin_tail) {
-      f32x16 o;
-      float ls[2] = {0.f, 0.f}, m0[2] = {0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < 16; ++j) o[j] = 0.f;
-      for (int w = 0; w < 4; ++w) {
-#pragma unroll
-        for (int j4 = 0; j4 < 4; ++j4) {
-          const float4 v = *slot(w, 8 + j4);
-          o[4 * j4] += v.x; o[4 * j4 + 1] += v.y; o[4 * j4 + 2] += v.z; o[4 * j4 + 3] += v.w;
-        }
-        const float4 lv = ps[(w * kF5Slots + 12) * 64 + 16 + ql];
-        ls[0] += lv.x;
-        ls[1] += lv.y;
-      }
-      bad2 |= store(nqb - 1, o, ls, m0, true, true);
-    }
-    const bool wave_bad = __builtin_amdgcn_ballot_w64(bad2) != 0;   // every lane votes (not under lane == 0)
-    if (lane == 0 && wave_bad) f5_flag = 1;
-    __syncthreads();
-    if (f5_flag) {   // a rejected split block (vanishingly rare): K / V again, the block through the SAFE loop
-      gather();
-      __syncthreads();
-      if (__builtin_amdgcn_ballot_w64(bad2) != 0) {
-        safe_block(fin_pair ? 2 * pa : nqb - 1);
-        if (fin_pair) safe_block(2 * pa + 1);
-      }
-    }
-  }
+  const int nw = dfk_bdim() >> 6, ngrp = (nqb + 1) / 2, qstep = nw * qsplit;
+  for (int gi = wu.qpart * nw + wave; gi < ngrp; gi += qstep) full(2 * gi, 2 * gi + 1);
 }
 
 size_t fwd_lds_bf16(const dfk_wattn_args& a, const Geo& g) {
@@ -2089,27 +1930,68 @@ size_t fwd_lds(const dfk_wattn_args& a, const Geo& g) {
   return sizeof(TokInfo) * g.Np + 4 * (size_t)((g.L + 3) & ~3) + (size_t)g.Np * a.hd * es + v;
 }
 
-}  // namespace
+// Launch KFN with up to 160 KiB of dynamic LDS.  The limit is raised once per kernel, on its first launch: the
+// helper is keyed on the function itself, because the instantiations of one kernel template share a function type.
+// That first launch must never fall inside a graph capture — callers warm every kernel up before they capture.
+template <auto KFN, typename... Args>
+void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+  static const bool attr_set =
+      ((void)hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);
+  (void)attr_set;
+  hipLaunchKernelGGL(KFN, grid, block, lds, s, args...);
+}
 
-// dfk_wattn_fwd_policy (DFK_WATTN_V / DFK_WATTN_BALMIN set the start values for A/B runs)
-// defaults: v6; the balanced schedule from 512 units for v5, off for v6 (measured slower there: r5h, stage 1
-// 189.9 vs 178.5 us — the split phase's extra Q loads, barriers and spills cost more than the idle wave)
-static int g_fwd_version = getenv("DFK_WATTN_V") ? atoi(getenv("DFK_WATTN_V")) : 6;
-static long g_fwd_bal_min = getenv("DFK_WATTN_BALMIN") ? atol(getenv("DFK_WATTN_BALMIN")) : -1;   // -1: default
+// the backward kernels that sweep the queries in chunks of Qn rows: one launch per chunk (q0, rows, accumulate flag)
+template <auto KFN, typename... Args>
+void launch_chunks(int Qn, dim3 grid, dim3 block, size_t lds, hipStream_t s, const dfk_wattn_bwd_args& ba,
+                   const Geo& g, const Args&... tail) {
+  for (int q0 = 0; q0 < g.Np; q0 += Qn)
+    launch_lds<KFN>(grid, block, lds, s, ba, g, q0, std::min(Qn, g.Np - q0), q0 > 0 ? 1 : 0, tail...);
+}
 
-// the forward reads its bias tiles in the 16x16x32 layout (wattn_fwd6_kernel) — the same predicate as dfk_wattn_fwd
+// the bias-table path of dfk_wattn_fwd / dfk_wattn_bwd (v3 and later kernels): bf16, no explicit mask, and either
+// the tiles of dfk_wattn_table (RPB and / or shift mask) or no bias at all
+bool has_bias(const dfk_wattn_args& a, const Geo& g) { return a.rpb || g.use_mask; }
+bool table_path(const dfk_wattn_args& a, const Geo& g) {
+  return a.dtype == DFK_BF16 && !a.mask && a.scale > 0.f && (a.tab || !has_bias(a, g));
+}
+
+// windows of shift class c per clip (a class bit needs its dim shifted, and then marks the last window along it),
+// as decode_unit and decode_group count them
+long class_windows(const dfk_wattn_args& a, const Geo& g, int c) {
+  const long nd = g.use_mask ? ((c & 4) ? (a.sd > 0) : g.nwd - (a.sd > 0)) : g.nwd;
+  const long nh = g.use_mask ? ((c & 2) ? (a.sh > 0) : g.nwh - (a.sh > 0)) : g.nwh;
+  const long nw = g.use_mask ? ((c & 1) ? (a.sw > 0) : g.nww - (a.sw > 0)) : g.nww;
+  return nd * nh * nw;
+}
+
+// Forward kernel for the hd-32 bias-table windows: 6, 5 or 4, and the smallest launch (units) that runs v5 on its
+// balanced schedule (-1: kV5BalMinUnits) — dfk_wattn_fwd_policy
+int g_fwd_version = 6;
+long g_fwd_bal_min = -1;
+constexpr long kV5BalMinUnits = 512;
+// dfk_wattn_bwd_policy: the backward kernel for v6's windows (4: two-pass, 3: single-pass everywhere) and the
+// windows per work group of the two-pass kernel (0: bwd3_group's rule)
+int g_bwd_version = 4;
+int g_bwd_group = 0;
+
 // v6 runs windows of at least 4 query blocks (Np >= 128: every Video Swin stage); the 49-token SwinV2 windows keep
 // v4 — v6 gains nothing there (mel1: 14.5-15.7 vs 15.5 us) and v4's rounding keeps the SwinV2 logit_scale gradients
 // where the goldens hold them (r5j: C1 mel layers.1.blocks.1 logit_scale norm 5.7 % with v4, 8.6 % with v6, against
 // 1.1 % in the reference's own bf16 run — the same attention error, rms 2.8e-3 either way, tools/wattn_err.py, in a
 // gradient that cancels to a few % of its terms)
-static const int g_v6_min_qb = getenv("DFK_WATTN_V6MIN") ? atoi(getenv("DFK_WATTN_V6MIN")) : 4;   // A/B runs only
-static const int g_v6_ones = getenv("DFK_WATTN_ONES") ? atoi(getenv("DFK_WATTN_ONES")) : 0;      // A/B runs only
-static const int g_v6_w8 = getenv("DFK_WATTN_W8") ? atoi(getenv("DFK_WATTN_W8")) : 0;            // A/B runs only
-static bool use_v6(const dfk_wattn_args& a, const Geo& g) {
-  return g_fwd_version == 6 && a.hd == 32 && !a.drop.mode && g.Np / 32 >= g_v6_min_qb;
+constexpr int kV6MinQb = 4;
+// query blocks per wave of the hd-32 table kernels: K / V fragment reads shared, two chains interleaved (the
+// kernels are latency-bound: r4f ablations, profiles/attn/r4f_fwd4_ablations.txt)
+constexpr int kFwdQGroup = 2;
+
+// v6 runs this geometry (given bias tables), so its tiles are in the 16x16x32 layout: dfk_wattn_table,
+// dfk_wattn_fwd and the backward's two-pass kernel all decide by this one predicate
+bool use_v6(const dfk_wattn_args& a, const Geo& g) {
+  return g_fwd_version == 6 && a.hd == 32 && !a.drop.mode && g.Np / 32 >= kV6MinQb;
 }
-static bool fwd16_layout(const dfk_wattn_args& a, const Geo& g) { return use_v6(a, g); }
+
+}  // namespace
 
 extern "C" int dfk_wattn_table(const dfk_wattn_args* ap, hipStream_t s) {
   if (!ap || !args_ok(*ap) || !ap->tab || ap->dtype != DFK_BF16 || ap->mask || !(ap->scale > 0.f)) return DFK_EINVAL;
@@ -2121,12 +2003,8 @@ extern "C" int dfk_wattn_table(const dfk_wattn_args* ap, hipStream_t s) {
   // uses 2 of the 8): the 192-channel stage-4 table took 125 us for 384 window-heads
   ClsMap cm{};
   int nc = 0;
-  for (int c = 0; c < tg.ncls; ++c) {
-    const long nd = !g.use_mask ? g.nwd : ((c & 4) ? (a.sd > 0) : g.nwd - (a.sd > 0));
-    const long nh = !g.use_mask ? g.nwh : ((c & 2) ? (a.sh > 0) : g.nwh - (a.sh > 0));
-    const long nw = !g.use_mask ? g.nww : ((c & 1) ? (a.sw > 0) : g.nww - (a.sw > 0));
-    if (nd * nh * nw > 0) cm.c[nc++] = c;
-  }
+  for (int c = 0; c < tg.ncls; ++c)
+    if (class_windows(a, g, c) > 0) cm.c[nc++] = c;
   if (nc == 0) return 0;
   // about eight 16-B slots per thread (the per-workgroup prologue — token labels, the head's RPB column —
   // amortised), unless that leaves fewer than 1024 workgroups (the small SwinV2 tables)
@@ -2134,12 +2012,10 @@ extern "C" int dfk_wattn_table(const dfk_wattn_args* ap, hipStream_t s) {
   long gx = std::min<long>(dfk_cdiv(slots2, 256 * 8), 64);
   if (gx * nc * a.heads < 1024) gx = std::min<long>(dfk_cdiv(slots2, 256), std::max<long>(gx, dfk_cdiv(1024, nc * a.heads)));
   hipLaunchKernelGGL(wattn_tab3_kernel, dim3((unsigned)gx, nc * a.heads),
-                     dim3(256), 4 * (size_t)(g.Np + g.L), s, a, g, t3, t3 + tab_elems(a, g), fwd16_layout(a, g) ? 1 : 0,
-                     cm);
+                     dim3(256), 4 * (size_t)(g.Np + g.L), s, a, g, t3, t3 + tab_elems(a, g), use_v6(a, g) ? 1 : 0, cm);
   DFK_CHECK_LAUNCH();
   return 0;
 }
-
 
 extern "C" int dfk_wattn_fwd_policy(int32_t version, int64_t bal_min_units) {
   if (version >= 0) g_fwd_version = version;
@@ -2152,120 +2028,79 @@ extern "C" int dfk_wattn_fwd(const dfk_wattn_args* ap, hipStream_t s) {
   const dfk_wattn_args& a = *ap;
   const Geo g = make_geo(a);
   if (a.drop.mode && !(a.dtype == DFK_BF16 && !a.mask && a.scale > 0.f)) return DFK_EINVAL;  // bf16 v3 path only
-  if (a.dtype == DFK_BF16 && !a.mask && a.scale > 0.f && (a.tab || (!a.rpb && !g.use_mask))) {
-    // v3: bias tiles from dfk_wattn_table (RPB and / or shift mask), or no bias at all
-    const long units = (long)a.B * g.nW * a.heads;
+  const long units = (long)a.B * g.nW * a.heads;
+  if (table_path(a, g)) {
     if (units <= 0) return 0;
-    const bool tab = a.rpb || g.use_mask;
+    const bool tab = has_bias(a, g);
     const bf16raw* t3 = tab ? tab3_fwd(a, g) : nullptr;
     const size_t lds = 4 * (size_t)g.Np * a.hd;
     if (lds > 160 * 1024) return DFK_EINVAL;
     const int nqb = g.Np / 32;
-    // query blocks per wave: 2 for the hd-32 table kernel (K / V fragment reads shared, two chains interleaved)
-    static const int qgrp_env = getenv("DFK_WATTN_QB") ? atoi(getenv("DFK_WATTN_QB")) : 2;   // A/B runs only
-    const int qgrp = tab && a.hd == 32 && !a.drop.mode && nqb >= 2 ? qgrp_env : 1;
+    const int qgrp = tab && a.hd == 32 && !a.drop.mode && nqb >= 2 ? kFwdQGroup : 1;
     const int ngrp = dfk_cdiv(nqb, qgrp);
-    const bool w8 = g_v6_w8 && tab && qgrp == 2 && use_v6(a, g);
-    const int nw = std::min(w8 ? 8 : 4, ngrp);
+    const int nw = std::min(4, ngrp);
     int qsplit = (int)std::max<long>(1, std::min<long>(dfk_cdiv(ngrp, nw), dfk_cdiv(1024, units)));
-    // v5 (no running max; A/B: DFK_WATTN_V=4 keeps v4) and its balanced schedule (one workgroup per unit, the
-    // remaining pairs and the tail split by keys over the 4 waves) from DFK_WATTN_BALMIN units (default 512)
-    const bool v6 = tab && qgrp == 2 && use_v6(a, g);
-    const bool v5 = tab && a.hd == 32 && !a.drop.mode && qgrp == 2 && g_fwd_version == 5;   // v4 otherwise
-    const int pairs = nqb / 2;
-    const long bal_min = g_fwd_bal_min >= 0 ? g_fwd_bal_min : (v5 ? 512 : LONG_MAX);
-    const bool bal = (v5 || v6) && !w8 && nw == 4 && pairs % 4 != 3 && units >= bal_min;
-    size_t lds_k = lds;
+    // v5 (dfk_wattn_fwd_policy version 5) and its balanced schedule: one workgroup per unit, the remaining pairs
+    // and the tail split by keys over the 4 waves, the partials meeting in LDS
+    const bool v5 = qgrp == 2 && g_fwd_version == 5;
+    const bool bal = v5 && nw == 4 && (nqb / 2) % 4 != 3 && units >= (g_fwd_bal_min >= 0 ? g_fwd_bal_min : kV5BalMinUnits);
+    size_t lds_bal = 0;
     if (bal) {
       qsplit = 1;
-      lds_k = std::max(lds, (size_t)4 * kF5Slots * 64 * 16) + 16;   // + the fallback flag
+      lds_bal = std::max(lds, (size_t)4 * kF5Slots * 64 * 16) + 16;   // + the fallback flag
     }
-    dim3 grid((unsigned)(units * qsplit));
-#define LAUNCH_K(KFN)                                                                                        \
-  do {                                                                                                       \
-    auto kfn = KFN;                                                                                          \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kfn, grid, dim3(64 * nw), lds_k, s, a, g, qsplit, t3);                               \
-  } while (0)
-    // bias tables: v4 (bias through the QK^T C input, VALU row sums); no bias: v3's table-free form
+    const dim3 grid((unsigned)(units * qsplit)), block(64 * nw);
+    // bias tables: v6 / v5 / v4 (bias through the QK^T C input, VALU row sums); no bias: v3
+    const bool drop = a.drop.mode != 0;
     if (a.hd == 32) {
-      if (tab) {
-        if (a.drop.mode) LAUNCH_K((wattn_fwd4_kernel<32, true, 1>));
-        else if (v6 && bal) LAUNCH_K((wattn_fwd6_kernel<true>));
-        else if (v6 && g_v6_w8) LAUNCH_K((wattn_fwd6_kernel<false, false, true>));
-        else if (v6 && g_v6_ones) LAUNCH_K((wattn_fwd6_kernel<false, true>));
-        else if (v6) LAUNCH_K((wattn_fwd6_kernel<false>));
-        else if (bal) LAUNCH_K((wattn_fwd5_kernel<true>));
-        else if (v5) LAUNCH_K((wattn_fwd5_kernel<false>));
-        else if (qgrp == 2) LAUNCH_K((wattn_fwd4_kernel<32, false, 2>));
-        else LAUNCH_K((wattn_fwd4_kernel<32, false, 1>));
-      } else {
-        if (a.drop.mode) LAUNCH_K((wattn_fwd3_kernel<32, false, true>)); else LAUNCH_K((wattn_fwd3_kernel<32, false, false>));
-      }
+      if (!tab && drop) launch_lds<wattn_fwd3_kernel<32, true>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (!tab) launch_lds<wattn_fwd3_kernel<32, false>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (drop) launch_lds<wattn_fwd4_kernel<32, true, 1>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (use_v6(a, g)) launch_lds<wattn_fwd6_kernel>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (bal) launch_lds<wattn_fwd5_kernel<true>>(grid, block, lds_bal, s, a, g, qsplit, t3);
+      else if (v5) launch_lds<wattn_fwd5_kernel<false>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (qgrp == 2) launch_lds<wattn_fwd4_kernel<32, false, 2>>(grid, block, lds, s, a, g, qsplit, t3);
+      else launch_lds<wattn_fwd4_kernel<32, false, 1>>(grid, block, lds, s, a, g, qsplit, t3);
     } else {
-      if (tab) {
-        if (a.drop.mode) LAUNCH_K((wattn_fwd4_kernel<64, true, 1>)); else LAUNCH_K((wattn_fwd4_kernel<64, false, 1>));
-      } else {
-        if (a.drop.mode) LAUNCH_K((wattn_fwd3_kernel<64, false, true>)); else LAUNCH_K((wattn_fwd3_kernel<64, false, false>));
-      }
+      if (!tab && drop) launch_lds<wattn_fwd3_kernel<64, true>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (!tab) launch_lds<wattn_fwd3_kernel<64, false>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (drop) launch_lds<wattn_fwd4_kernel<64, true, 1>>(grid, block, lds, s, a, g, qsplit, t3);
+      else launch_lds<wattn_fwd4_kernel<64, false, 1>>(grid, block, lds, s, a, g, qsplit, t3);
     }
-#undef LAUNCH_K
     DFK_CHECK_LAUNCH();
     return 0;
   }
-  if (a.dtype == DFK_BF16) {
+  if (a.dtype == DFK_BF16) {   // the gather kernels: an explicit mask, or RPB / shift mask without tables
     const size_t lds = fwd_lds_bf16(a, g);
     if (lds > 160 * 1024) return DFK_EINVAL;
-    const long units = (long)a.B * g.nW * a.heads;
     if (units <= 0) return 0;
     const int nqb = g.Np / 32;
     const int nw = std::min(4, nqb);   // small windows (SwinV2 7x7: two query blocks) get fewer waves
     const int qsplit = (int)std::max<long>(1, std::min<long>(dfk_cdiv(nqb, nw), dfk_cdiv(1024, units)));
-    dim3 grid((unsigned)units, qsplit);
-#define LAUNCH_F16(HD, RPB, MASK)                                                                          \
-  do {                                                                                                     \
-    auto kfn = wattn_fwd_bf16_kernel<HD, RPB, MASK>;                                                       \
-    static bool attr_set = false;                                                                          \
-    if (!attr_set) {                                                                                       \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr_set = true;                                                                                     \
-    }                                                                                                      \
-    hipLaunchKernelGGL(kfn, grid, dim3(64 * nw), lds, s, a, g, qsplit);                                    \
-  } while (0)
-#define PICK_F16(HD)                                                                            \
-  do {                                                                                          \
-    if (a.rpb) { if (a.mask) LAUNCH_F16(HD, true, true); else LAUNCH_F16(HD, true, false); }   \
-    else { if (a.mask) LAUNCH_F16(HD, false, true); else LAUNCH_F16(HD, false, false); }       \
-  } while (0)
-    if (a.hd == 32) PICK_F16(32); else PICK_F16(64);
-#undef PICK_F16
-#undef LAUNCH_F16
+    const dim3 grid((unsigned)units, qsplit), block(64 * nw);
+    const bool rpb = a.rpb != nullptr, mask = a.mask != nullptr;
+    if (a.hd == 32) {
+      if (rpb && mask) launch_lds<wattn_fwd_bf16_kernel<32, true, true>>(grid, block, lds, s, a, g, qsplit);
+      else if (rpb) launch_lds<wattn_fwd_bf16_kernel<32, true, false>>(grid, block, lds, s, a, g, qsplit);
+      else if (mask) launch_lds<wattn_fwd_bf16_kernel<32, false, true>>(grid, block, lds, s, a, g, qsplit);
+      else launch_lds<wattn_fwd_bf16_kernel<32, false, false>>(grid, block, lds, s, a, g, qsplit);
+    } else {
+      if (rpb && mask) launch_lds<wattn_fwd_bf16_kernel<64, true, true>>(grid, block, lds, s, a, g, qsplit);
+      else if (rpb) launch_lds<wattn_fwd_bf16_kernel<64, true, false>>(grid, block, lds, s, a, g, qsplit);
+      else if (mask) launch_lds<wattn_fwd_bf16_kernel<64, false, true>>(grid, block, lds, s, a, g, qsplit);
+      else launch_lds<wattn_fwd_bf16_kernel<64, false, false>>(grid, block, lds, s, a, g, qsplit);
+    }
     DFK_CHECK_LAUNCH();
     return 0;
   }
   const size_t lds = fwd_lds(a, g);
   if (lds > 160 * 1024) return DFK_EINVAL;
-  const long units = (long)a.B * g.nW * a.heads;
   if (units <= 0) return 0;
   const int nqt = dfk_cdiv(g.N, 16);
-  int qsplit = (int)std::max<long>(1, std::min<long>(dfk_cdiv(nqt, 4), dfk_cdiv(1024, units)));
-  dim3 grid((unsigned)units, qsplit);
-#define LAUNCH_F(T, HD)                                                                                 \
-  do {                                                                                                  \
-    auto kfn = wattn_fwd_kernel<T, HD>;                                                                 \
-    static bool attr_set = false;  /* once per kernel: the 160 KiB LDS limit (never inside a capture) */ \
-    if (!attr_set) {                                                                                    \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr_set = true;                                                                                  \
-    }                                                                                                   \
-    hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, a, g, qsplit);                                     \
-  } while (0)
-  if (a.hd == 32) LAUNCH_F(float, 32); else LAUNCH_F(float, 64);
-#undef LAUNCH_F
+  const int qsplit = (int)std::max<long>(1, std::min<long>(dfk_cdiv(nqt, 4), dfk_cdiv(1024, units)));
+  const dim3 grid((unsigned)units, qsplit);
+  if (a.hd == 32) launch_lds<wattn_fwd_kernel<float, 32>>(grid, dim3(256), lds, s, a, g, qsplit);
+  else launch_lds<wattn_fwd_kernel<float, 64>>(grid, dim3(256), lds, s, a, g, qsplit);
   DFK_CHECK_LAUNCH();
   return 0;
 }
@@ -3723,10 +3558,9 @@ size_t bwd4_lds(const Geo& g) { return (size_t)g.Np * (8 * 32 + 12); }
 
 // the two-pass kernel's geometry (bf16 bias tables of the v6 forward layout, hd 32, no dropout); it alone groups
 // windows into shared dRPB slabs (wattn_bwd3's read-modify-write of the slab, behind a branch, stalled each step)
-extern int g_bwd_version;
 bool bwd4_geometry(const dfk_wattn_args& a, const Geo& g) {
-  return g_bwd_version == 4 && a.dtype == DFK_BF16 && !a.mask && a.scale > 0.f && a.tab && a.hd == 32 &&
-         !a.drop.mode && fwd16_layout(a, g) && bwd4_lds(g) <= 160 * 1024 && 2 * (g.Np / 32) <= 48;   // B4Sched
+  return g_bwd_version == 4 && table_path(a, g) && a.tab && a.hd == 32 && !a.drop.mode && use_v6(a, g) &&
+         bwd4_lds(g) <= 160 * 1024 && 2 * (g.Np / 32) <= 48;   // B4Sched
 }
 
 size_t bwd3_lds(const dfk_wattn_args& a, const Geo& g, int Qn, int nw, bool cos = false) {
@@ -3820,54 +3654,38 @@ struct DsPlan {
   long rows;       // workspace rows of L floats
 };
 
-// windows per backward work group (wattn_bwd3_kernel, decode_group): enough groups left for ~3 rounds of one
-// workgroup per CU (768), at most 8 (DFK_DRPB_G: A/B runs only)
-int g_bwd_group = getenv("DFK_DRPB_G") ? atoi(getenv("DFK_DRPB_G")) : 0;   // dfk_wattn_bwd_policy
-int g_bwd_version = getenv("DFK_WATTN_BWD") ? atoi(getenv("DFK_WATTN_BWD")) : 4;
-// bwd4's unit assignment (B4Sched): the smallest makespan over the waves for unit costs cA (a pass-A key block) and
-// cB (a pass-B query block) — units of one pass are interchangeable, so a plan is a count (a_w, b_w) per wave, found by
-// a DP per candidate makespan (DFK_B4_SCHED=0: round robin; DFK_B4_COST="cA,cB", default 4,3 products per step)
+// bwd4's unit assignment (B4Sched): the smallest makespan over the waves for unit costs kB4CostA (a pass-A key block)
+// and kB4CostB (a pass-B query block), in MFMA products per step — units of one pass are interchangeable, so a plan
+// is a count (a_w, b_w) per wave, found by a DP per candidate makespan
+constexpr int kB4CostA = 4, kB4CostB = 3;
 B4Sched b4_sched(int nb) {
-  static const int mode = getenv("DFK_B4_SCHED") ? atoi(getenv("DFK_B4_SCHED")) : 1;   // A/B runs only
-  static int cA = 4, cB = 3;
-  static const bool parsed = [] {
-    if (const char* e = getenv("DFK_B4_COST")) {
-      int x = 0, y = 0;
-      if (sscanf(e, "%d,%d", &x, &y) == 2 && x > 0 && y > 0) { cA = x; cB = y; }
-    }
-    return true;
-  }();
-  (void)parsed;
+  constexpr int cA = kB4CostA, cB = kB4CostB;
   constexpr int W = kB4Waves;
   int na[W] = {}, nbw[W] = {};
-  if (mode == 0) {
-    for (int u = 0; u < 2 * nb; ++u) (u < nb ? na : nbw)[u % W] += 1;
-  } else {
-    // smallest T such that W waves hold nb A units and nb B units with cA a_w + cB b_w <= T
-    for (int T = ((nb * (cA + cB)) + W - 1) / W;; ++T) {
-      int cap[W + 1][64];   // cap[w][a] = max B units the first w waves hold with a A units among them (-1: none)
-      for (int w = 0; w <= W; ++w)
-        for (int a = 0; a <= nb; ++a) cap[w][a] = -1;
-      cap[0][0] = 0;
-      for (int w = 0; w < W; ++w)
-        for (int a = 0; a <= nb; ++a) {
-          if (cap[w][a] < 0) continue;
-          for (int x = 0; a + x <= nb && cA * x <= T; ++x)
-            cap[w + 1][a + x] = std::max(cap[w + 1][a + x], cap[w][a] + (T - cA * x) / cB);
-        }
-      if (cap[W][nb] < nb) continue;
-      // walk back: choose a_w per wave (any choice that keeps the rest feasible), b_w greedily
-      int a = nb, b = nb;
-      for (int w = W - 1; w >= 0; --w) {
-        for (int x = 0; x <= a && cA * x <= T; ++x) {
-          const int prev = cap[w][a - x];
-          if (prev < 0) continue;
-          const int take = std::min(b, (T - cA * x) / cB);
-          if (prev >= b - take) { na[w] = x; nbw[w] = take; a -= x; b -= take; break; }
-        }
+  // smallest T such that W waves hold nb A units and nb B units with cA a_w + cB b_w <= T
+  for (int T = ((nb * (cA + cB)) + W - 1) / W;; ++T) {
+    int cap[W + 1][64];   // cap[w][a] = max B units the first w waves hold with a A units among them (-1: none)
+    for (int w = 0; w <= W; ++w)
+      for (int a = 0; a <= nb; ++a) cap[w][a] = -1;
+    cap[0][0] = 0;
+    for (int w = 0; w < W; ++w)
+      for (int a = 0; a <= nb; ++a) {
+        if (cap[w][a] < 0) continue;
+        for (int x = 0; a + x <= nb && cA * x <= T; ++x)
+          cap[w + 1][a + x] = std::max(cap[w + 1][a + x], cap[w][a] + (T - cA * x) / cB);
       }
-      break;
+    if (cap[W][nb] < nb) continue;
+    // walk back: choose a_w per wave (any choice that keeps the rest feasible), b_w greedily
+    int a = nb, b = nb;
+    for (int w = W - 1; w >= 0; --w) {
+      for (int x = 0; x <= a && cA * x <= T; ++x) {
+        const int prev = cap[w][a - x];
+        if (prev < 0) continue;
+        const int take = std::min(b, (T - cA * x) / cB);
+        if (prev >= b - take) { na[w] = x; nbw[w] = take; a -= x; b -= take; break; }
+      }
     }
+    break;
   }
   B4Sched sc{};
   uint8_t* by = reinterpret_cast<uint8_t*>(sc.w);
@@ -3886,22 +3704,16 @@ int bwd3_group(const dfk_wattn_args& a, const Geo& g) {
   // Step-level sweep (round 6, full training step, same box): G=8 280.0 clips/s, G=6 275.2, G=12 274.2,
   // G=16 268.8, G=32 233.8, old auto rule (units/768, 4/2/1 per stage) 271.4. Fewer, longer
   // workgroups overlap better with the branch streams than the isolated kernel time suggests.
-  static const long minwg = getenv("DFK_DRPB_GMINWG") ? atol(getenv("DFK_DRPB_GMINWG")) : 64;   // A/B runs only
-  static const long gmax = getenv("DFK_DRPB_GMAX") ? atol(getenv("DFK_DRPB_GMAX")) : 8;         // A/B runs only
+  constexpr long kGroupMax = 8, kGroupMinWg = 64;   // at most 8 windows per group, at least 64 workgroups left
   const long units = (long)a.B * g.nW * a.heads;
-  return (int)std::max<long>(1, std::min<long>(gmax, units / std::max<long>(1, minwg)));
+  return (int)std::max<long>(1, std::min<long>(kGroupMax, units / kGroupMinWg));
 }
 
 // dS^T slabs per head (window groups over the shift classes, as decode_group counts them)
 long bwd3_slab_windows(const dfk_wattn_args& a, const Geo& g, int G) {
   const int ncls = g.use_mask ? 8 : 1;
   long tot = 0;
-  for (int c = 0; c < ncls; ++c) {
-    const long nd = g.use_mask ? ((c & 4) ? (a.sd > 0) : g.nwd - (a.sd > 0)) : g.nwd;
-    const long nh = g.use_mask ? ((c & 2) ? (a.sh > 0) : g.nwh - (a.sh > 0)) : g.nwh;
-    const long nw = g.use_mask ? ((c & 1) ? (a.sw > 0) : g.nww - (a.sw > 0)) : g.nww;
-    tot += dfk_cdiv(nd * nh * nw * a.B, (long)G);
-  }
+  for (int c = 0; c < ncls; ++c) tot += dfk_cdiv(class_windows(a, g, c) * a.B, (long)G);
   return tot;
 }
 
@@ -3938,6 +3750,19 @@ void reduce_drpb(const dfk_wattn_bwd_args& ba, const Geo& g, long units, hipStre
                      ba.f.heads, g.L, ba.drpb);
 }
 
+// the bf16 kernels' dRPB tail: the dS^T slabs at the head of ba.ws (nwin per head) -> partial rows behind them ->
+// ba.drpb.  tiled: the slabs are in wattn_bwd4's tile order (drpb_from_ds_kernel)
+void drpb_from_slabs(const dfk_wattn_bwd_args& ba, const Geo& g, long nwin, int tiled, hipStream_t s) {
+  const dfk_wattn_args& a = ba.f;
+  const DsPlan pl = ds_plan(a, g, nwin);
+  const bf16raw* ds = reinterpret_cast<const bf16raw*>(ba.ws);
+  float* rows = reinterpret_cast<float*>(reinterpret_cast<char*>(ba.ws) + ((pl.ds_elems * 2 + 15) & ~15L));
+  hipLaunchKernelGGL(drpb_from_ds_kernel, dim3(pl.nchunks, a.heads, pl.nsplit), dim3(256), ((g.L + 3) & ~3) * 4, s,
+                     ds, nwin * a.heads, a.heads, g.Np, g.N, a.fh, a.fw, g.C0, g.L, pl.wps, rows, tiled);
+  hipLaunchKernelGGL(drpb_reduce_kernel, dim3(dfk_cdiv(g.L, 64), a.heads), dim3(1024), 0, s, rows, pl.rows, a.heads,
+                     g.L, ba.drpb);
+}
+
 }  // namespace
 
 extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
@@ -3946,11 +3771,11 @@ extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
   const int vec = a.dtype == DFK_BF16 ? 8 : 4;
   if (bp->ld_dqkv % vec || bp->ld_dout % vec) return DFK_EINVAL;
   const Geo g = make_geo(a);
-  if (a.dtype == DFK_BF16 && !a.mask && a.scale > 0.f && (a.tab || (!a.rpb && !g.use_mask))) {
+  const long units = (long)a.B * g.nW * a.heads;
+  if (table_path(a, g)) {
     // v3 (the forward's bias tiles, bwd layout)
-    const long units = (long)a.B * g.nW * a.heads;
     if (units <= 0) return 0;
-    const bool tab = a.rpb || g.use_mask;
+    const bool tab = has_bias(a, g);
     const bf16raw* tb = tab ? tab3_fwd(a, g) + tab_elems(a, g) : nullptr;
     const int nkb = g.Np / 32;
     int nw = dfk_cdiv(nkb, dfk_cdiv(nkb, 8));   // passes of at most 8 waves, balanced
@@ -3971,48 +3796,26 @@ extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
     if (v4 && cos) return DFK_EINVAL;   // dscore: the single-pass kernel (SwinV2's 49-token windows) only
     const int G = v4 ? bwd3_group(a, g) : 1;
     const long slabw = bwd3_slab_windows(a, g, G);
+    const dim3 grid((unsigned)(slabw * a.heads));
+    const dim3 block(64 * nw);
+    const bool drop = a.drop.mode != 0;
     if (v4) {   // the two-pass kernel (the v6 windows)
-      static bool attr4 = false;
-      if (!attr4) {
-        (void)hipFuncSetAttribute((const void*)wattn_bwd4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr4 = true;
-      }
-      hipLaunchKernelGGL(wattn_bwd4_kernel, dim3((unsigned)(slabw * a.heads)), dim3(64 * kB4Waves), bwd4_lds(g), s,
-                         *bp, g, dsg, tab3_fwd(a, g), tb, G, b4_sched(g.Np / 32));
+      launch_lds<wattn_bwd4_kernel>(grid, dim3(64 * kB4Waves), bwd4_lds(g), s, *bp, g, dsg, tab3_fwd(a, g), tb, G,
+                                    b4_sched(g.Np / 32));
+    } else if (a.hd == 32) {
+      if (cos) launch_chunks<wattn_bwd3_kernel<32, true, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (tab && drop) launch_chunks<wattn_bwd3_kernel<32, true, true, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (tab) launch_chunks<wattn_bwd3_kernel<32, true, false, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (drop) launch_chunks<wattn_bwd3_kernel<32, false, true, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else launch_chunks<wattn_bwd3_kernel<32, false, false, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+    } else {
+      if (cos) launch_chunks<wattn_bwd3_kernel<64, true, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (tab && drop) launch_chunks<wattn_bwd3_kernel<64, true, true, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (tab) launch_chunks<wattn_bwd3_kernel<64, true, false, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (drop) launch_chunks<wattn_bwd3_kernel<64, false, true, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else launch_chunks<wattn_bwd3_kernel<64, false, false, false>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
     }
-#define LAUNCH_B3(HD, TB, DR, CS)                                                                          \
-  do {                                                                                                     \
-    auto kfn = wattn_bwd3_kernel<HD, TB, DR, CS>;                                                            \
-    static bool attr_set = false;                                                                          \
-    if (!attr_set) {                                                                                       \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr_set = true;                                                                                     \
-    }                                                                                                      \
-    for (int q0 = 0; q0 < g.Np; q0 += Qn)                                                                  \
-      hipLaunchKernelGGL(kfn, dim3((unsigned)(slabw * a.heads)), dim3(64 * nw), lds, s, *bp, g, q0,        \
-                         std::min(Qn, g.Np - q0), q0 > 0 ? 1 : 0, dsg, tb, G);                             \
-  } while (0)
-#define PICK_B3(HD)                                                                            \
-  do {                                                                                         \
-    if (cos) LAUNCH_B3(HD, true, false, true);                                                 \
-    else if (tab) { if (a.drop.mode) LAUNCH_B3(HD, true, true, false); else LAUNCH_B3(HD, true, false, false); } \
-    else { if (a.drop.mode) LAUNCH_B3(HD, false, true, false); else LAUNCH_B3(HD, false, false, false); }        \
-  } while (0)
-    if (!v4) {
-      if (a.hd == 32) PICK_B3(32); else PICK_B3(64);
-    }
-#undef PICK_B3
-#undef LAUNCH_B3
-    if (want_drpb) {
-      const DsPlan pl = ds_plan(a, g, slabw);
-      float* rows = reinterpret_cast<float*>(reinterpret_cast<char*>(bp->ws) + ((pl.ds_elems * 2 + 15) & ~15L));
-      hipLaunchKernelGGL(drpb_from_ds_kernel, dim3(pl.nchunks, a.heads, pl.nsplit), dim3(256),
-                         ((g.L + 3) & ~3) * 4, s, dsg, slabw * a.heads, a.heads, g.Np, g.N, a.fh, a.fw, g.C0, g.L,
-                         pl.wps, rows, v4 ? 1 : 0);
-      hipLaunchKernelGGL(drpb_reduce_kernel, dim3(dfk_cdiv(g.L, 64), a.heads), dim3(1024), 0, s, rows, pl.rows,
-                         a.heads, g.L, bp->drpb);
-    }
+    if (want_drpb) drpb_from_slabs(*bp, g, slabw, v4 ? 1 : 0, s);
     DFK_CHECK_LAUNCH();
     return 0;
   }
@@ -4023,41 +3826,25 @@ extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
     while (Qn > 32 && bwd_lds_bf16(a, g, Qn, nwaves) > 160 * 1024) Qn -= 32;
     const size_t lds = bwd_lds_bf16(a, g, Qn, nwaves);
     if (lds > 160 * 1024) return DFK_EINVAL;
-    const long units = (long)a.B * g.nW * a.heads;
     if (units <= 0) return 0;
-#define LAUNCH_B16(HD, RPB, MASK)                                                                          \
-  do {                                                                                                     \
-    auto kfn = wattn_bwd_bf16_kernel<HD, RPB, MASK>;                                                       \
-    static bool attr_set = false;                                                                          \
-    if (!attr_set) {                                                                                       \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr_set = true;                                                                                     \
-    }                                                                                                      \
-    for (int q0 = 0; q0 < g.Np; q0 += Qn)                                                                  \
-      hipLaunchKernelGGL(kfn, dim3((unsigned)units), dim3(64 * nwaves), lds, s, *bp, g, q0,                \
-                         std::min(Qn, g.Np - q0), q0 > 0 ? 1 : 0, dsg);                                    \
-  } while (0)
-#define PICK_B16(HD)                                                 \
-  do {                                                               \
-    if (a.rpb) { if (a.mask) LAUNCH_B16(HD, true, true); else LAUNCH_B16(HD, true, false); } \
-    else { if (a.mask) LAUNCH_B16(HD, false, true); else LAUNCH_B16(HD, false, false); }     \
-  } while (0)
     const bool want_drpb = a.rpb && bp->drpb;
     if (want_drpb && !bp->ws) return DFK_EINVAL;  // dRPB needs the dfk_wattn_bwd_workspace scratch
-    const DsPlan pl = ds_plan(a, g, units / a.heads);
     bf16raw* dsg = want_drpb ? reinterpret_cast<bf16raw*>(bp->ws) : nullptr;
     if (a.drop.mode) return DFK_EINVAL;   // attention dropout: v3 kernels only (as the forward)
-    if (a.hd == 32) PICK_B16(32); else PICK_B16(64);
-#undef PICK_B16
-#undef LAUNCH_B16
-    if (want_drpb) {
-      float* rows = reinterpret_cast<float*>(reinterpret_cast<char*>(bp->ws) + ((pl.ds_elems * 2 + 15) & ~15L));
-      hipLaunchKernelGGL(drpb_from_ds_kernel, dim3(pl.nchunks, a.heads, pl.nsplit), dim3(256),
-                         ((g.L + 3) & ~3) * 4, s, dsg, units, a.heads, g.Np, g.N, a.fh, a.fw, g.C0, g.L, pl.wps,
-                         rows, 0);
-      hipLaunchKernelGGL(drpb_reduce_kernel, dim3(dfk_cdiv(g.L, 64), a.heads), dim3(1024), 0, s, rows, pl.rows,
-                         a.heads, g.L, bp->drpb);
+    const dim3 grid((unsigned)units), block(64 * nwaves);
+    const bool rpb = a.rpb != nullptr, mask = a.mask != nullptr;
+    if (a.hd == 32) {
+      if (rpb && mask) launch_chunks<wattn_bwd_bf16_kernel<32, true, true>>(Qn, grid, block, lds, s, *bp, g, dsg);
+      else if (rpb) launch_chunks<wattn_bwd_bf16_kernel<32, true, false>>(Qn, grid, block, lds, s, *bp, g, dsg);
+      else if (mask) launch_chunks<wattn_bwd_bf16_kernel<32, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg);
+      else launch_chunks<wattn_bwd_bf16_kernel<32, false, false>>(Qn, grid, block, lds, s, *bp, g, dsg);
+    } else {
+      if (rpb && mask) launch_chunks<wattn_bwd_bf16_kernel<64, true, true>>(Qn, grid, block, lds, s, *bp, g, dsg);
+      else if (rpb) launch_chunks<wattn_bwd_bf16_kernel<64, true, false>>(Qn, grid, block, lds, s, *bp, g, dsg);
+      else if (mask) launch_chunks<wattn_bwd_bf16_kernel<64, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg);
+      else launch_chunks<wattn_bwd_bf16_kernel<64, false, false>>(Qn, grid, block, lds, s, *bp, g, dsg);
     }
+    if (want_drpb) drpb_from_slabs(*bp, g, units / a.heads, 0, s);
     DFK_CHECK_LAUNCH();
     return 0;
   }
@@ -4067,22 +3854,10 @@ extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
   while (Qn > 32 && bwd_lds(a, g, Qn) > 160 * 1024) Qn -= 32;
   const size_t lds = bwd_lds(a, g, Qn);
   if (lds > 160 * 1024) return DFK_EINVAL;
-  const long units = (long)a.B * g.nW * a.heads;
   if (units <= 0) return 0;
-  dim3 grid((unsigned)units);
-#define LAUNCH_B(T, HD)                                                                                 \
-  do {                                                                                                  \
-    auto kfn = wattn_bwd_kernel<T, HD>;                                                                 \
-    static bool attr_set = false;  /* once per kernel: the 160 KiB LDS limit (never inside a capture) */ \
-    if (!attr_set) {                                                                                    \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr_set = true;                                                                                  \
-    }                                                                                                   \
-    for (int q0 = 0; q0 < g.Np; q0 += Qn)                                                               \
-      hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, *bp, g, q0, std::min(Qn, g.Np - q0), q0 > 0 ? 1 : 0); \
-  } while (0)
-  if (a.hd == 32) LAUNCH_B(float, 32); else LAUNCH_B(float, 64);
-#undef LAUNCH_B
+  const dim3 grid((unsigned)units), block(256);
+  if (a.hd == 32) launch_chunks<wattn_bwd_kernel<float, 32>>(Qn, grid, block, lds, s, *bp, g);
+  else launch_chunks<wattn_bwd_kernel<float, 64>>(Qn, grid, block, lds, s, *bp, g);
   reduce_drpb(*bp, g, units, s);
   DFK_CHECK_LAUNCH();
   return 0;
@@ -4092,7 +3867,7 @@ extern "C" int64_t dfk_wattn_table_workspace(const dfk_wattn_args* f) {
   if (!f || !args_ok(*f)) return -1;
   if (f->dtype != DFK_BF16 || f->mask) return 0;
   const Geo g = make_geo(*f);
-  if (!f->rpb && !g.use_mask) return 0;   // no bias at all (wav2vec2): the kernels mask the padded keys themselves
+  if (!has_bias(*f, g)) return 0;   // no bias at all (wav2vec2): the kernels mask the padded keys themselves
   return tab3_bytes(*f, g);   // bf16 fwd + bwd layouts
 }
 

@@ -444,10 +444,9 @@ def window_attention(qkv, rpb, qkv_bias, geo, mask=None, drop=None, dscore=None)
 def dscore_buffer(owner, qkv, heads, drop):
     """The [heads] fp32 buffer through which the attention backward hands sum dS * score to CosineQKFn's backward
     (dfk_wattn_bwd_args.dscore), or None where the attention kernel cannot produce it (fp32 parity mode, attention
-    dropout, the table path switched off): CosineQKFn then derives the logit_scale gradient from q-hat . dq'.
+    dropout): CosineQKFn then derives the logit_scale gradient from q-hat . dq'.
     Persistent per module (zeroed once; the consumer re-zeroes it), so a captured step holds no fill for it."""
-    if qkv.dtype != torch.bfloat16 or drop is not None or os.environ.get("DFK_WATTN_TABLE", "1") == "0" \
-            or os.environ.get("DFK_COS_DSCORE", "0") != "1":
+    if qkv.dtype != torch.bfloat16 or drop is not None or os.environ.get("DFK_COS_DSCORE", "0") != "1":
         return None
     buf = getattr(owner, "_dfk_dscore", None)
     if buf is None or buf.device != qkv.device or buf.numel() != heads:

@@ -423,7 +423,7 @@ def wattn_fwd(q, k, v, ld_qkv, dims, window, full_window, shift, heads, hd, scal
                    drop)
     if tab is not None:
         a.tab = tab.data_ptr()
-    elif use_table and os.environ.get("DFK_WATTN_TABLE", "1") != "0":
+    elif use_table:
         nbytes = L.lib().dfk_wattn_table_workspace(a)
         if nbytes < 0:
             raise RuntimeError("dfk_wattn_table_workspace: invalid arguments")
@@ -439,8 +439,9 @@ def wattn_fwd(q, k, v, ld_qkv, dims, window, full_window, shift, heads, hd, scal
 
 def wattn_fwd_policy(version=-1, bal_min_units=-1):
     """Process-wide kernel choice of the hd-32 bf16 table forward (tests / A/B runs): version 6 (no running max,
-    16x16x32 tiles, default), 5 (32x32x16) or 4 (max-subtracted); bal_min_units = smallest launch on the balanced
-    key-split schedule. -1 leaves a setting, -2 restores the default.  The bias table must be built under the same policy as the forward."""
+    16x16x32 tiles, default), 5 (32x32x16) or 4 (max-subtracted); bal_min_units = smallest launch that runs
+    version 5 on its balanced key-split schedule.  -1 leaves a setting, -2 restores the default.  The bias table
+    must be built under the same policy as the forward."""
     L.check(L.lib().dfk_wattn_fwd_policy(int(version), int(bal_min_units)), "wattn_fwd_policy")
 
 

@@ -143,14 +143,14 @@ V5_CASES = [
     ((1, 3, 14, 14), (3, 7, 7), (1, 3, 3), 2),    # N 147: 5 blocks, pairs 2 (R 2) + tail
     ((1, 4, 14, 14), (4, 7, 7), (2, 3, 3), 2),    # N 196: 7 blocks, pairs 3 (R 3: simple schedule)
 ]
-V5_POLICIES = [(5, 0), (5, 1 << 40), (4, -1), (6, 0), (6, 1 << 40)]   # v5 balanced / simple, v4, v6 balanced / simple
+V5_POLICIES = [(5, 0), (5, 1 << 40), (4, -1), (6, 1 << 40)]   # v5 balanced / simple, v4, v6 (one schedule)
 
 
-@pytest.mark.parametrize("policy", V5_POLICIES, ids=["v5bal", "v5", "v4", "v6bal", "v6"])
+@pytest.mark.parametrize("policy", V5_POLICIES, ids=["v5bal", "v5", "v4", "v6"])
 @pytest.mark.parametrize("extreme", ["normal", "huge", "tiny"])
 @pytest.mark.parametrize("case", V5_CASES, ids=[str(i) for i in range(len(V5_CASES))])
 def test_wattn_fwd_v5(case, extreme, policy):
-    """bf16 table forward, every schedule of the no-running-max kernel against the fp32 reference.  'huge'
+    """bf16 table forward, every forward policy (v5 on both its schedules) against the fp32 reference.  'huge'
     scores (up to ~±600 log2 units) and 'tiny' rows (every score ~ -150 log2 units) are rejected by the fast
     path's l in [2^-80, 2^100] test and recomputed by the max-subtracted loop: the output is still the softmax."""
     dims, window, shift, heads = case

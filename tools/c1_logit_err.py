@@ -1,7 +1,6 @@
 """C1 bf16 training step: the SwinV2 logit_scale gradient norms against the reference's fp32 step and the
 reference's own bf16 error (tests/golden/fused_c1.npz gn:*, fused_c1_grads.npz ea:*), plus the worst tensor
-overall.  A/B: DFK_COS_DSCORE=0 (q-hat . dq' in the cosine backward), DFK_WATTN_V6MIN (v6 from that many
-query blocks; 2 puts the 49-token SwinV2 windows on v6)."""
+overall.  A/B: DFK_COS_DSCORE=0 (q-hat . dq' in the cosine backward)."""
 import os
 import sys
 
@@ -23,7 +22,7 @@ m.train()
 p = m((video.cuda(), mel.cuda(), wave.cuda()))
 torch.nn.BCELoss()(p.float(), label.cuda()).backward()
 names = dict(m.named_parameters())
-tag = f"dscore={os.environ.get('DFK_COS_DSCORE', '1')} v6min={os.environ.get('DFK_WATTN_V6MIN', '4')}"
+tag = f"dscore={os.environ.get('DFK_COS_DSCORE', '1')}"
 worst = (None, 0.0, 0.0)
 for k in keys(fx, "gn:"):
     n = k[3:]
