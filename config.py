@@ -19,6 +19,11 @@
                            --adam_beta1, --adam_beta2, --adam_eps set its other hyper-parameters
   --clip_grad_norm FLOAT   global gradient-norm clipping (torch.nn.utils.clip_grad_norm_ on the mean gradient right
                            before the step) fused into either optimizer on the device; 0 (default): off
+  --no_decay {none,norm_bias}   parameter groups of either optimizer: norm_bias takes 1-D parameters (norm gains,
+                           biases) and the Swin position parameters (relative_position_bias_table, absolute_pos_embed,
+                           cpb_mlp, logit_scale) out of --l2_decacy; none (default): the reference's single group
+  --lr_scale PREFIX=MULT   learning-rate multiplier for the parameters whose name starts with PREFIX (the longest
+                           matching prefix wins), repeatable: --lr_scale vExtract=0.1 --lr_scale aExtract=0.1
   --ema_decay FLOAT        exponential moving average of the weights, updated on the device right after every
                            optimizer step (inside the captured step); validation, submission and the checkpoint's
                            "checkpoint_ema" use the averaged weights; 0 (default): off.  --ema_warmup ramps the decay
@@ -100,6 +105,12 @@ def build_parser():
     parser.add_argument('--adam_eps', type=float, default=1e-8)
     parser.add_argument('--clip_grad_norm', type=float, default=0.0,
                         help='max global gradient norm (clip_grad_norm_ semantics, on the device); 0: no clipping')
+    parser.add_argument('--no_decay', type=str, default='none', choices=['none', 'norm_bias'],
+                        help='norm_bias: no weight decay on 1-D parameters and the Swin position parameters '
+                             '(per-group weight decay in the fused optimizer); none: one group')
+    parser.add_argument('--lr_scale', action='append', default=[], metavar='PREFIX=MULT',
+                        help='learning-rate multiplier for the parameters whose name starts with PREFIX; repeatable, '
+                             'the longest matching prefix wins')
     parser.add_argument('--ema_decay', type=float, default=0.0,
                         help='decay of the weight EMA kept on the device, in [0, 1) (e.g. 0.9999); validation, '
                              'submission and the checkpoint use the averaged weights; 0: no EMA')

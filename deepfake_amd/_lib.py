@@ -133,6 +133,9 @@ SIGNATURES = {
     "dfk_adamw_step": [_VP, _VP, _VP, _VP, _VP, _I64, _VP, _F, C.c_double, C.c_double, _F, _F, _VP, _VP, _F, _VP, _VP],
     "dfk_adamw_step_runs": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _F, C.c_double, C.c_double, _F, _F, _VP, _I32,
                             _F, _VP, _VP],
+    "dfk_sgd_step_runs_groups": [_VP, _VP, _VP, _VP, _VP, _I32, _VP, _F, _F, _VP, _I64, _VP, _I32, _F, _VP, _VP, _VP],
+    "dfk_adamw_step_runs_groups": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _F, C.c_double, C.c_double, _F, _VP, _I32,
+                                   _VP, _I64, _VP, _I32, _F, _VP, _VP, _VP],
     "dfk_grad_sqnorm_runs": [_VP, _VP, _VP, _I32, _F, _VP, _VP],
     "dfk_grad_clip_coef": [_VP, _I32, _F, _VP, _VP],
     "dfk_ema_prelude": [_VP, _VP, C.c_double, _I32, _VP],

@@ -1,5 +1,6 @@
 // The optimizer: fused SGD and AdamW steps over the flat fp32 parameter store (one run per launch, or every run of
-// the step in one launch through a by-value run table) and global gradient-norm clipping.  All HBM-bound: 16-B
+// the step in one launch through a by-value run table, also with a learning-rate multiplier and a weight decay per
+// parameter group looked up per quad) and global gradient-norm clipping.  All HBM-bound: 16-B
 // quads of the fp32 buffers, 8-B quads of the bf16 ones, the n % 4 tail of a run one element at a time.
 // Shared by every kernel here:
 //   gate: a LayerDrop-skipped layer (*gate == 0) is left untouched, as torch skips grad=None parameters.
@@ -365,6 +366,150 @@ __global__ __launch_bounds__(256) void adamw_runs_kernel(float* __restrict__ P, 
   }
 }
 
+// Parameter groups (the dfk_*_step_runs_groups entry points): the twins of sgd_runs_kernel / adamw_runs_kernel with
+// the learning-rate multiplier and the weight decay looked up per quad instead of taken from the launch arguments, so
+// that groups which alternate tensor by tensor along the store do not split the runs.
+//   map:   one byte per 8 elements of the store (every parameter starts on a multiple of 8, run starts and quads on
+//          multiples of 4: a quad lies in one cell; alignment padding shares the byte of the tensor it follows and
+//          holds p = g = m = v = 0, which stays 0 under any pair).  The byte is clamped to the table's last row: no
+//          value in that device array can take a read outside `hyper`.
+//   hyper: fp32 [ngroups][2] = {lr_mult, weight_decay} in device memory, read at every launch (a value changed
+//          between two replays of a captured step takes effect).
+// lr_e = lr * lr_mult is one rounded multiply (lr_mult == 1 gives lr's bits); given equal scalars the per-element
+// sequence is the plain kernels' own (the same *_load4 / *_update4 / *_tail), so one group is bit-equal to the twin.
+// The map bytes are issued ahead of the 16-B streams (with no branch around them, so nothing waits in between) and
+// the pair loads they select behind the streams.  As compiled, the per-quad branches around the streams make the wait
+// in front of the pair loads cover most of the streams too; a whole-block path without those branches, where the
+// pairs go out under the streams, measured the same on the C2 store (profiles/optim/groups_timing.md).
+struct GroupTab {
+  const uint8_t* map;
+  const float* hyper;
+  int32_t last;                       // ngroups - 1
+};
+
+__device__ __forceinline__ float2 group_pair(const GroupTab& T, int byte) {
+  return *reinterpret_cast<const float2*>(T.hyper + 2 * min(byte, T.last));
+}
+
+__device__ __forceinline__ float group_lr(float lr, float mult) {
+#pragma clang fp contract(off)
+  return lr * mult;
+}
+
+__device__ __forceinline__ SgdRun sgd_group_run(SgdRun r, float lr, float2 hy) {
+  r.lr = group_lr(lr, hy.x);
+  r.wd = hy.y;
+  return r;
+}
+
+template <bool CLIP>
+__global__ __launch_bounds__(256) void sgd_runs_groups_kernel(float* __restrict__ P, const float* __restrict__ G,
+                                                              float* __restrict__ Bf, bf16raw* __restrict__ S,
+                                                              const SgdRuns R, const float* __restrict__ lr_dev,
+                                                              float lr_host, float mom, float gscale,
+                                                              const bf16raw* __restrict__ GB,
+                                                              const float* __restrict__ clip, const GroupTab T) {
+  const int b = blockIdx.x;
+  const int run = find_run(R.prefix, R.nruns, b);
+  const long start = R.start[run], n = R.n[run];
+  const float* gate = R.gate[run];
+  const int first = (int)((R.first >> run) & 1);
+  if (gate && *gate == 0.f) return;
+  const float lr = lr_dev ? *lr_dev : lr_host;
+  float gmul = gscale;
+  if constexpr (CLIP) gmul = gscale * *clip;
+  const SgdRun r{P + start, G + start, Bf + start, S ? S + start : nullptr, GB ? GB + start : nullptr, n, 0.f, mom,
+                 0.f, gmul, first};                      // lr and wd come per quad
+  const long base = (long)(b - R.prefix[run]) * kRunBlock;
+  const long idx[2] = {base + threadIdx.x * 4, base + 1024 + threadIdx.x * 4};
+  SgdQuad q[2];
+  bool full[2];
+  int byte[2];
+  float2 hy[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {     // the map bytes, then both quads' loads, then the pairs the bytes select
+    full[u] = idx[u] + 4 <= n;
+    byte[u] = T.map[(start + (full[u] ? idx[u] : 0)) >> 3];   // no branch around it: the run's first cell otherwise
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (full[u]) sgd_load4(r, idx[u], q[u]);
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (full[u]) hy[u] = group_pair(T, byte[u]);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (full[u]) {
+      sgd_update4(sgd_group_run(r, lr, hy[u]), idx[u], q[u]);
+    } else {
+      for (long i = idx[u]; i < n; ++i) {        // the tail: each element takes the byte of its own index
+        SgdRun e = sgd_group_run(r, lr, group_pair(T, T.map[(start + i) >> 3]));
+        e.n = i + 1;
+        sgd_tail(e, i);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ AdamwRun adamw_group_run(AdamwRun r, float lr, float c1, float2 hy) {
+#pragma clang fp contract(off)
+  const float lr_e = group_lr(lr, hy.x);
+  r.decay = (float)(1.0 - (double)lr_e * (double)hy.y);
+  r.step = lr_e * c1;
+  return r;
+}
+
+template <bool CLIP>
+__global__ __launch_bounds__(256) void adamw_runs_groups_kernel(float* __restrict__ P, const float* __restrict__ G,
+                                                                float* __restrict__ M, float* __restrict__ V,
+                                                                bf16raw* __restrict__ S, const AdamwRuns R,
+                                                                const float* __restrict__ lr_dev, float lr_host,
+                                                                const AdamwHyper h, const float* __restrict__ corr,
+                                                                const bf16raw* __restrict__ GB,
+                                                                const float* __restrict__ clip, const GroupTab T) {
+  const int b = blockIdx.x;
+  const int run = find_run(R.prefix, R.nruns, b);
+  const long start = R.start[run], n = R.n[run];
+  const float* gate = R.gate[run];
+  if (gate && *gate == 0.f) return;
+  const float* cr = corr + 2 * R.cls[run];
+  const float lr = lr_dev ? *lr_dev : lr_host;
+  const float c1 = cr[0];
+  float coef = 1.f;
+  if constexpr (CLIP) coef = *clip;
+  const AdamwRun r{P + start, G + start, M + start, V + start, S ? S + start : nullptr, GB ? GB + start : nullptr,
+                   n, 1.f, 0.f, cr[1], coef};            // decay and step come per quad
+  const long base = (long)(b - R.prefix[run]) * kRunBlock;
+  const long idx[2] = {base + threadIdx.x * 4, base + 1024 + threadIdx.x * 4};
+  AdamwQuad q[2];
+  bool full[2];
+  int byte[2];
+  float2 hy[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {     // as sgd_runs_groups_kernel
+    full[u] = idx[u] + 4 <= n;
+    byte[u] = T.map[(start + (full[u] ? idx[u] : 0)) >> 3];
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (full[u]) adamw_load4(r, idx[u], q[u]);
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (full[u]) hy[u] = group_pair(T, byte[u]);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (full[u]) {
+      adamw_update4<CLIP>(adamw_group_run(r, lr, c1, hy[u]), idx[u], q[u], h);
+    } else {
+      for (long i = idx[u]; i < n; ++i) {
+        AdamwRun e = adamw_group_run(r, lr, c1, group_pair(T, T.map[(start + i) >> 3]));
+        e.n = i + 1;
+        adamw_tail<CLIP>(e, i, h);
+      }
+    }
+  }
+}
+
 // Global gradient norm (torch.nn.utils.clip_grad_norm_, norm_type 2), stage 1: sum of (g * gscale)^2 over the
 // runs of the step, g read as the update kernels read it (fp32, or the bf16 bucket copy).  A fixed grid of
 // kGnormPartials persistent workgroups; workgroup w owns the kRunBlock-element blocks w, w + kGnormPartials, ...
@@ -543,6 +688,20 @@ int adamw_step_runs_impl(float* param, const float* grad, float* exp_avg, float*
   return 0;
 }
 
+// The groups arguments of a *_runs_groups entry point (the run table already filled): false for a NULL or, for the
+// pairs, not 8-B aligned table, ngroups outside 1..256, or a map shorter than the runs reach
+bool fill_group_tab(GroupTab& T, const RunTable& R, const uint8_t* group_map, int64_t map_len,
+                    const float* group_hyper, int32_t ngroups) {
+  if (!group_map || !group_hyper || ngroups < 1 || ngroups > 256) return false;
+  if (reinterpret_cast<uintptr_t>(group_hyper) & 7) return false;
+  int64_t end = 0;
+  for (int r = 0; r < R.nruns; ++r)
+    if (R.start[r] + R.n[r] > end) end = R.start[r] + R.n[r];
+  if (map_len < (end + 7) / 8) return false;
+  T = GroupTab{group_map, group_hyper, ngroups - 1};
+  return true;
+}
+
 }  // namespace
 
 extern "C" int dfk_sgd_step(float* param, const float* grad, float* momentum_buf, void* bf16_shadow, int64_t n,
@@ -575,6 +734,28 @@ extern "C" int dfk_sgd_step_runs_clip(float* param, const float* grad, float* mo
   if (!clip_coef || nruns < 1 || nruns > kMaxRuns) return DFK_EINVAL;
   return sgd_step_runs_impl(param, grad, momentum_buf, bf16_shadow, runs, nruns, lr_dev, lr, momentum, weight_decay,
                             grad_scale, grad_bf16, clip_coef, s);
+}
+
+extern "C" int dfk_sgd_step_runs_groups(float* param, const float* grad, float* momentum_buf, void* bf16_shadow,
+                                        const int64_t* runs, int32_t nruns, const float* lr_dev, float lr,
+                                        float momentum, const uint8_t* group_map, int64_t map_len,
+                                        const float* group_hyper, int32_t ngroups, float grad_scale,
+                                        const void* grad_bf16, const float* clip_coef, hipStream_t s) {
+  if (!param || !grad || !momentum_buf || !runs || nruns <= 0) return DFK_EINVAL;
+  if (nruns > kMaxRuns) return DFK_ENOTSUP;
+  if (misaligned({param, grad, momentum_buf}, {grad_bf16, bf16_shadow})) return DFK_EINVAL;
+  SgdRuns R{};
+  GroupTab T{};
+  if (!fill_run_table(R, runs, nruns) || !fill_group_tab(T, R, group_map, map_len, group_hyper, ngroups))
+    return DFK_EINVAL;
+  for (int r = 0; r < nruns; ++r)
+    if (runs[4 * r + 3]) R.first |= 1ull << r;
+  hipLaunchKernelGGL(clip_coef ? sgd_runs_groups_kernel<true> : sgd_runs_groups_kernel<false>,
+                     dim3((unsigned)R.prefix[nruns]), dim3(256), 0, s, param, grad, momentum_buf,
+                     (bf16raw*)bf16_shadow, R, lr_dev, lr, momentum, grad_scale, (const bf16raw*)grad_bf16, clip_coef,
+                     T);
+  DFK_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int dfk_adamw_prelude(int32_t* counters, float* corr, int32_t nclass, const int64_t* classes, int32_t n,
@@ -631,6 +812,33 @@ extern "C" int dfk_adamw_step_runs_clip(float* param, const float* grad, float* 
   if (!clip_coef || nruns < 1 || nruns > kMaxRuns) return DFK_EINVAL;
   return adamw_step_runs_impl(param, grad, exp_avg, exp_avg_sq, bf16_shadow, runs, nruns, lr_dev, lr, b1, b2, eps,
                               weight_decay, corr, nclass, grad_scale, grad_bf16, clip_coef, s);
+}
+
+extern "C" int dfk_adamw_step_runs_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                          void* bf16_shadow, const int64_t* runs, int32_t nruns, const float* lr_dev,
+                                          float lr, double b1, double b2, float eps, const float* corr,
+                                          int32_t nclass, const uint8_t* group_map, int64_t map_len,
+                                          const float* group_hyper, int32_t ngroups, float grad_scale,
+                                          const void* grad_bf16, const float* clip_coef, hipStream_t s) {
+  AdamwHyper h;
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !corr || !runs || nruns <= 0 || nclass <= 0) return DFK_EINVAL;
+  if (!adamw_hyper(b1, b2, eps, 0.f, grad_scale, &h)) return DFK_EINVAL;     // the decay comes from group_hyper
+  if (nruns > kMaxRuns || nclass > kAdamwMaxClasses) return DFK_ENOTSUP;
+  if (misaligned({param, grad, exp_avg, exp_avg_sq}, {grad_bf16, bf16_shadow})) return DFK_EINVAL;
+  AdamwRuns R{};
+  GroupTab T{};
+  if (!fill_run_table(R, runs, nruns) || !fill_group_tab(T, R, group_map, map_len, group_hyper, ngroups))
+    return DFK_EINVAL;
+  for (int r = 0; r < nruns; ++r) {
+    const int64_t c = runs[4 * r + 3];
+    if (c < 0 || c >= nclass) return DFK_EINVAL;
+    R.cls[r] = (uint8_t)c;
+  }
+  hipLaunchKernelGGL(clip_coef ? adamw_runs_groups_kernel<true> : adamw_runs_groups_kernel<false>,
+                     dim3((unsigned)R.prefix[nruns]), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq,
+                     (bf16raw*)bf16_shadow, R, lr_dev, lr, h, corr, (const bf16raw*)grad_bf16, clip_coef, T);
+  DFK_CHECK_LAUNCH();
+  return 0;
 }
 
 // Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_(params, max_norm, 2.0, error_if_nonfinite=False) on

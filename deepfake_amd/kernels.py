@@ -741,6 +741,47 @@ def adamw_step_runs(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps,
 adamw_step_runs_clip = _clip_twin(adamw_step_runs)
 
 
+GROUPS_MAX = 256         # rows of group_hyper (one map byte selects a row)
+GROUP_CELL = 8           # elements of the store per map byte (params._ALIGN)
+
+
+def _group_args(group_map, group_hyper, runs, clip_coef, what):
+    """(map, map_len, hyper, ngroups) and the clip pointer (None: no clipping) of a *_runs_groups launch."""
+    if group_map.dtype != torch.uint8 or not group_map.is_contiguous() or \
+            group_map.numel() < -(-max(e for _, e, _, _ in runs) // GROUP_CELL):
+        raise ValueError(f"{what}: group_map is uint8, one byte per {GROUP_CELL} elements up to the last run's end")
+    if group_hyper.dtype != torch.float32 or group_hyper.dim() != 2 or group_hyper.shape[1] != 2 or \
+            not group_hyper.is_contiguous() or not 0 < group_hyper.shape[0] <= GROUPS_MAX:
+        raise ValueError(f"{what}: group_hyper is fp32 [1..{GROUPS_MAX}][2] = (lr_mult, weight_decay)")
+    if clip_coef is not None:
+        _clip_args(clip_coef, what)
+    return (L.ptr(group_map), group_map.numel(), L.ptr(group_hyper), group_hyper.shape[0]), _opt(clip_coef)
+
+
+def sgd_step_runs_groups(param, grad, buf, shadow, runs, momentum, lr_dev, group_map, group_hyper, grad_scale=1.0,
+                         grad_bf16=None, clip_coef=None):
+    """sgd_step_runs with the learning-rate multiplier and the weight decay per parameter group: group_map (device
+    uint8, one byte per 8 elements of the store) selects the row {lr_mult, weight_decay} of group_hyper (device fp32
+    [ngroups][2]) for every quad.  clip_coef: as sgd_step_runs (None: no clipping)."""
+    tab = _run_table([(s, e, g, bool(f)) for s, e, g, f in runs], "sgd_step_runs_groups")
+    ga, clip = _group_args(group_map, group_hyper, runs, clip_coef, "sgd_step_runs_groups")
+    L.check(L.lib().dfk_sgd_step_runs_groups(L.ptr(param), L.ptr(grad), L.ptr(buf), _opt(shadow), tab, len(runs),
+                                             L.ptr(lr_dev), 0.0, float(momentum), *ga, float(grad_scale),
+                                             _opt(grad_bf16), clip, L.stream()), "sgd_step_runs_groups")
+
+
+def adamw_step_runs_groups(param, grad, exp_avg, exp_avg_sq, shadow, runs, b1, b2, eps, lr_dev, corr, group_map,
+                           group_hyper, grad_scale=1.0, grad_bf16=None, clip_coef=None):
+    """adamw_step_runs with the learning-rate multiplier and the weight decay per parameter group (group_map /
+    group_hyper as sgd_step_runs_groups)."""
+    tab = _run_table(runs, "adamw_step_runs_groups")
+    ga, clip = _group_args(group_map, group_hyper, runs, clip_coef, "adamw_step_runs_groups")
+    L.check(L.lib().dfk_adamw_step_runs_groups(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
+                                               _opt(shadow), tab, len(runs), L.ptr(lr_dev), 0.0, float(b1), float(b2),
+                                               float(eps), L.ptr(corr), corr.numel() // 2, *ga, float(grad_scale),
+                                               _opt(grad_bf16), clip, L.stream()), "adamw_step_runs_groups")
+
+
 def grad_sqnorm_runs(grad, runs, partials, grad_scale=1.0, grad_bf16=None):
     """Sum of (g * grad_scale)^2 over the runs [(start, end, gate tensor or None)], g read from grad_bf16 when
     given: chunks of 64 runs, chunk k into partials[k * GNORM_PARTIALS : (k + 1) * GNORM_PARTIALS] (fp64, every

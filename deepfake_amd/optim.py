@@ -13,6 +13,10 @@ kernels that multiply the gradient by the coefficient they read from device memo
 ParamEMA: an exponential moving average of the whole flat store, updated by one kernel right after the optimizer step
 (its update count and decay warm-up in device memory, so it replays inside the captured step) and exchanged with the
 live weights for evaluation, so the model itself evaluates through the average ("Weight EMA").
+ParamGroups (both optimizers, groups=): a learning-rate multiplier and a weight decay per group of parameters, as
+torch.optim's param groups (no decay on norm / bias / position parameters, another lr for the new head), looked up
+per quad by the dfk_*_step_runs_groups kernels through a byte map of the store, so the groups split no run
+("Parameter groups").
 """
 import contextlib
 import math
@@ -27,6 +31,82 @@ from . import kernels as K
 _RUNS = os.environ.get("DFK_SGD_RUNS", "1") != "0"
 
 
+NO_DECAY_KEYWORDS = ("relative_position_bias_table", "absolute_pos_embed", "cpb_mlp", "logit_scale")
+
+
+class ParamGroups:
+    """Which (lr multiplier, weight decay) every parameter of a ParamStore takes.
+
+    no_decay: "none" — every parameter decays by `weight_decay` (torch's single group); "norm_bias" — weight decay 0
+      for a parameter with ndim <= 1 (LayerNorm / BatchNorm gains and biases, every bias) or whose name contains one
+      of NO_DECAY_KEYWORDS: the no_weight_decay() / no_weight_decay_keywords() sets of the Swin and SwinV2 recipes.
+    lr_scale: {name prefix: multiplier}; a parameter takes the multiplier of the longest prefix its name starts with,
+      1.0 without one.  A prefix that matches no parameter, and a multiplier that is not finite or <= 0, raise.
+    The groups are the distinct (multiplier, decay) pairs in the order model.named_parameters() first shows them, at
+    most 256.  Built once: group_map (device uint8, one byte per 8 elements of the store: the group index of the
+    parameter that owns the cell, 0 in flat_groups() gaps) and group_hyper (device fp32 [groups][2] = (multiplier,
+    decay), read by the kernels at every launch, so an entry overwritten in place acts from the next step on, also in
+    a replayed graph).  param_groups is torch's list: {"lr", "initial_lr", "weight_decay", "lr_scale", "params":
+    [names]}; the two rates are None until an optimizer is built over the groups and fills them in."""
+
+    def __init__(self, model, store, weight_decay, no_decay="none", lr_scale=None):
+        if no_decay not in ("none", "norm_bias"):
+            raise ValueError(f"ParamGroups: no_decay is 'none' or 'norm_bias', got {no_decay!r}")
+        scale = {str(k): float(v) for k, v in (lr_scale or {}).items()}
+        for k, v in scale.items():
+            if not (math.isfinite(v) and v > 0.0):
+                raise ValueError(f"ParamGroups: lr_scale[{k!r}] must be a positive finite multiplier, got {v}")
+        self.store, self.weight_decay, self.no_decay, self.lr_scale = store, float(weight_decay), no_decay, scale
+        used, keys, self.spec, members = set(), {}, {}, []
+        cell = K.GROUP_CELL
+        if any(o % cell for o in store.offsets):
+            raise ValueError(f"ParamGroups: the store places a parameter off a multiple of {cell} elements")
+        gmap = torch.zeros(-(-store.numel // cell), dtype=torch.uint8)
+        for name, p in model.named_parameters():
+            i = store.index.get(id(p))
+            if i is None or name in self.spec:
+                continue
+            hit = max((k for k in scale if name.startswith(k)), key=len, default=None)
+            used.add(hit)
+            exempt = no_decay == "norm_bias" and (p.ndim <= 1 or any(w in name for w in NO_DECAY_KEYWORDS))
+            pair = (scale[hit] if hit is not None else 1.0, 0.0 if exempt else self.weight_decay)
+            if pair not in keys:
+                if len(keys) == K.GROUPS_MAX:
+                    raise ValueError(f"ParamGroups: more than {K.GROUPS_MAX} distinct (lr_scale, weight_decay) pairs")
+                keys[pair] = len(keys)
+                members.append([])
+            members[keys[pair]].append(name)
+            self.spec[name] = pair
+            s, e = store.span(i)
+            gmap[s // cell:-(-e // cell)] = keys[pair]
+        unused = sorted(k for k in scale if k not in used)
+        if unused:
+            raise ValueError(f"ParamGroups: lr_scale prefix {unused[0]!r} matches no parameter")
+        dev = store.flat.device
+        self.group_map = gmap.to(dev)
+        self.group_hyper = torch.tensor(list(keys), dtype=torch.float32).reshape(-1, 2).to(dev)
+        self.param_groups = [{"lr": None, "initial_lr": None, "weight_decay": wd, "lr_scale": mult, "params": names}
+                             for (mult, wd), names in zip(keys, members)]
+
+    def bind(self, lr):
+        """The param_groups at base rate `lr` (an optimizer's constructor calls this)."""
+        for g in self.param_groups:
+            g["lr"] = g["initial_lr"] = float(lr) * g["lr_scale"]
+        return self.param_groups
+
+    def summary(self):
+        """[(lr_scale, weight_decay, tensors, elements)] per group, for the log."""
+        numel = {self.store.name(i): p.numel() for i, p in enumerate(self.store.params)}
+        return [(g["lr_scale"], g["weight_decay"], len(g["params"]), sum(numel[n] for n in g["params"]))
+                for g in self.param_groups]
+
+    def check_spec(self, spec, who):
+        """Raise unless `spec` (a state_dict's "groups") names this layout: the same parameters with the same pairs."""
+        got = None if spec is None else {k: (float(v[0]), float(v[1])) for k, v in spec.items()}
+        if got != self.spec:
+            raise ValueError(f"{who}.load_state_dict: the state's parameter groups were built for another layout")
+
+
 class _Fused:
     """What FusedSGD and FusedAdamW share: the store, the learning rate in device memory (a captured graph replays
     with the scheduler's current lr), and the device state of global-norm clipping, allocated once: the fp64 partial
@@ -34,12 +114,16 @@ class _Fused:
     step."""
     folds_grad = True   # step() takes the all-reduced sum and 1 / world itself (TrainStep._fold)
 
-    def __init__(self, store, lr, max_grad_norm):
+    def __init__(self, store, lr, max_grad_norm, groups=None):
         self.store = store
-        self.base_lr = float(lr)
+        self.base_lr = self.lr = float(lr)     # lr: the one device rate, before any group's multiplier
         dev = store.flat.device
         self.lr_dev = torch.full((1,), self.base_lr, device=dev, dtype=torch.float32)
-        self.param_groups = [{"lr": self.base_lr, "initial_lr": self.base_lr}]
+        if groups is not None and groups.store is not store:
+            raise ValueError(f"{type(self).__name__}: groups were built over another parameter store")
+        self.groups = groups
+        self.param_groups = [{"lr": self.base_lr, "initial_lr": self.base_lr}] if groups is None else \
+            groups.bind(self.base_lr)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.grad_norm = self._partials = None
         if self.max_grad_norm is None:
@@ -52,8 +136,22 @@ class _Fused:
         self.grad_norm = torch.zeros(2, device=dev, dtype=torch.float32)
 
     def set_lr(self, lr):
-        self.param_groups[0]["lr"] = float(lr)
+        """One device rate for every group (the kernels multiply by the group's lr_scale); each group's "lr" is the
+        rate it steps at."""
+        for g in self.param_groups:
+            g["lr"] = float(lr) * g.get("lr_scale", 1.0)
+        self.lr = float(lr)
         self.lr_dev.fill_(float(lr))
+
+    def _group_state(self):
+        return {} if self.groups is None else {"groups": dict(self.groups.spec)}
+
+    def _check_groups(self, sd):
+        if self.groups is not None:
+            self.groups.check_spec(sd.get("groups"), type(self).__name__)
+        elif sd.get("groups") is not None:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the state carries parameter groups, this "
+                             f"optimizer has none")
 
     def zero_grad(self):
         self.store.zero_grad()
@@ -74,8 +172,8 @@ class _Fused:
 
 
 class FusedSGD(_Fused):
-    def __init__(self, store, lr, momentum=0.9, weight_decay=0.0, max_grad_norm=None):
-        super().__init__(store, lr, max_grad_norm)
+    def __init__(self, store, lr, momentum=0.9, weight_decay=0.0, max_grad_norm=None, groups=None):
+        super().__init__(store, lr, max_grad_norm, groups)
         self.momentum, self.weight_decay = float(momentum), float(weight_decay)
         self.buf = torch.zeros_like(store.flat)
         self.first = True
@@ -86,7 +184,10 @@ class FusedSGD(_Fused):
         no weight decay and no momentum for them): every contiguous run in one dfk_sgd_step_runs launch (one
         dfk_sgd_step per run beyond 64 runs, or with DFK_SGD_RUNS=0).
         grad_scale / grad_bf16: the data-parallel fold of GradBucketer.finish(fold=True) — the gradient is the
-        all-reduced sum (in the fp32 buffer, or in the bf16 bucket copy) times 1 / world."""
+        all-reduced sum (in the fp32 buffer, or in the bf16 bucket copy) times 1 / world.
+        With groups (ParamGroups): the same runs through dfk_sgd_step_runs_groups, 64 per launch, each quad taking
+        its group's lr multiplier and weight decay (the constructor's weight_decay is not read); the norm of a
+        clipped step is over all groups; DFK_SGD_RUNS=0 is ignored (the groups kernels have no one-run form)."""
         st = self.store
         gates = {id(g): g for g in st.gate if g is not None}
         gkey = [id(g) if g is not None else None for g in st.gate]
@@ -102,6 +203,14 @@ class FusedSGD(_Fused):
         ck = {}
         if self.max_grad_norm is not None and runs:   # the norm of the same runs, gates and fold, then the _clip twins
             ck["clip_coef"] = self._clip([(s, e, gates.get(k)) for s, e, (f, k) in runs], grad_scale, grad_bf16)
+        if self.groups is not None:
+            tab = [(s, e, gates.get(k), f) for s, e, (f, k) in runs]
+            for c in range(0, len(tab), K.SGD_MAX_RUNS):
+                K.sgd_step_runs_groups(st.flat, st.grad, self.buf, st.shadow, tab[c:c + K.SGD_MAX_RUNS],
+                                       self.momentum, self.lr_dev, self.groups.group_map, self.groups.group_hyper,
+                                       grad_scale=grad_scale, grad_bf16=grad_bf16, **ck)
+            self.first = False
+            return
         if _RUNS and 0 < len(runs) <= K.SGD_MAX_RUNS:
             K.sgd_step_runs(st.flat, st.grad, self.buf, st.shadow, [(s, e, gates.get(k), f) for s, e, (f, k) in runs],
                             self.momentum, self.weight_decay, self.lr_dev, grad_scale=grad_scale,
@@ -115,7 +224,8 @@ class FusedSGD(_Fused):
         self.first = False
 
     def state_dict(self):
-        return {"momentum_buffer": self.buf, "lr": self.param_groups[0]["lr"], "first": self.first}
+        """With groups also "groups": {parameter name: (lr_scale, weight_decay)}, the layout the state belongs to."""
+        return {"momentum_buffer": self.buf, "lr": self.lr, "first": self.first, **self._group_state()}
 
 
 class FusedAdamW(_Fused):
@@ -127,11 +237,11 @@ class FusedAdamW(_Fused):
     (dfk_adamw_step_runs; one dfk_adamw_step per run beyond 64 runs).  A gated-off class keeps parameters, moments,
     shadow and counter, as torch leaves a grad=None parameter, so a layer dropped in step 1 takes t = 1 in step 2."""
 
-    def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    def __init__(self, store, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, groups=None):
         b1, b2 = float(betas[0]), float(betas[1])
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or not float(eps) > 0.0:
             raise ValueError(f"FusedAdamW: betas must lie in [0, 1) and eps be positive, got {betas}, {eps}")
-        super().__init__(store, lr, max_grad_norm)
+        super().__init__(store, lr, max_grad_norm, groups)
         self.betas, self.eps, self.weight_decay = (b1, b2), float(eps), float(weight_decay)
         dev = store.flat.device
         self.exp_avg = torch.zeros_like(store.flat)
@@ -153,7 +263,9 @@ class FusedAdamW(_Fused):
         a capture that ran no backward).  `first` is FusedSGD's and ignored: zero moments and the device counters
         need no first-step flag.  grad_scale / grad_bf16: the data-parallel fold, as FusedSGD.step.
         The ungated parameters share one counter, so each must be stepped in every step or in none: one whose
-        gradient appears or disappears between steps would need its own count (torch keeps one per parameter)."""
+        gradient appears or disappears between steps would need its own count (torch keeps one per parameter).
+        With groups (ParamGroups): the same runs through dfk_adamw_step_runs_groups, 64 per launch, as
+        FusedSGD.step."""
         st = self.store
         every = not any(st.touched)
         touched = [True] * len(st.params) if every else list(st.touched)
@@ -172,6 +284,14 @@ class FusedAdamW(_Fused):
         if self.max_grad_norm is not None:    # norm and coefficient first, then the prelude and the _clip twins
             ck["clip_coef"] = self._clip([(s, e, self.gates[c]) for s, e, c in runs], grad_scale, grad_bf16)
         K.adamw_prelude(self.counters, self.corr, [(c, self.gates[c]) for c in sorted({c for _, _, c in runs})], b1, b2)
+        if self.groups is not None:
+            tab = [(s, e, self.gates[c], c) for s, e, c in runs]
+            for k in range(0, len(tab), K.SGD_MAX_RUNS):
+                K.adamw_step_runs_groups(st.flat, st.grad, self.exp_avg, self.exp_avg_sq, st.shadow,
+                                         tab[k:k + K.SGD_MAX_RUNS], b1, b2, self.eps, self.lr_dev, self.corr,
+                                         self.groups.group_map, self.groups.group_hyper, grad_scale=grad_scale,
+                                         grad_bf16=grad_bf16, **ck)
+            return
         # DFK_SGD_RUNS=0 selects the per-run launches only for a clipped step (A/B of the _clip twins): without
         # clipping FusedAdamW has never read the variable, and its launches stay what they were
         if (_RUNS or not ck) and len(runs) <= K.SGD_MAX_RUNS:
@@ -186,22 +306,25 @@ class FusedAdamW(_Fused):
                          grad_bf16=self._cut(grad_bf16, s, e), **ck)
 
     def state_dict(self):
-        """The live state (as torch's): moments over the flat store, the per-class device step counts, lr and the
-        hyper-parameters."""
+        """The live state (as torch's): moments over the flat store, the per-class device step counts, lr (the one
+        device rate, before any group's multiplier) and the hyper-parameters; with groups also "groups": {parameter
+        name: (lr_scale, weight_decay)}."""
         return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.counters,
-                "lr": self.param_groups[0]["lr"], "base_lr": self.base_lr, "betas": self.betas, "eps": self.eps,
-                "weight_decay": self.weight_decay, "active": self.active}
+                "lr": self.lr, "base_lr": self.base_lr, "betas": self.betas, "eps": self.eps,
+                "weight_decay": self.weight_decay, "active": self.active, **self._group_state()}
 
     def load_state_dict(self, sd):
         if sd["exp_avg"].numel() != self.exp_avg.numel() or sd["step"].numel() != self.counters.numel():
             raise ValueError("FusedAdamW.load_state_dict: state of another parameter store")
+        self._check_groups(sd)
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.counters.copy_(sd["step"])
         self.betas, self.eps = (float(sd["betas"][0]), float(sd["betas"][1])), float(sd["eps"])
         self.weight_decay, self.base_lr = float(sd["weight_decay"]), float(sd["base_lr"])
         self.active = list(sd["active"]) if sd["active"] is not None else None
-        self.param_groups[0]["initial_lr"] = self.base_lr
+        for g in self.param_groups:
+            g["initial_lr"] = self.base_lr * g.get("lr_scale", 1.0)
         self.set_lr(sd["lr"])
 
 

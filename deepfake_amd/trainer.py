@@ -8,7 +8,8 @@ re-built MI355X-first:
 * parameters / gradients in flat buffers with a bf16 compute shadow
   (deepfake_amd.params), fused SGD(momentum 0.9, weight decay), or with
   --optimizer adamw fused AdamW (src/trainer.py:6,78), + CosineAnnealingLR
-  (src/trainer.py:80-85) with the lr in device memory; with --ema_decay an
+  (src/trainer.py:80-85) with the lr in device memory; with --no_decay /
+  --lr_scale per-group weight decay and learning rate; with --ema_decay an
   exponential moving average of the weights updated on the device after every
   optimizer step, which validation, submission and the checkpoint then use;
 * BCELoss on the sigmoid output (src/trainer.py:88,132), accuracy
@@ -29,7 +30,7 @@ import torch.distributed as dist
 from . import kernels as K
 from . import rng
 from .ddp import GradBucketer, fr_last_id, recorder_on
-from .optim import CosineAnnealingLR, FusedAdamW, FusedSGD, ParamEMA
+from .optim import CosineAnnealingLR, FusedAdamW, FusedSGD, ParamEMA, ParamGroups
 from .params import ParamStore
 from .utils import AverageMeter, Logger
 
@@ -94,6 +95,24 @@ def ema_arg(args):
     if not math.isfinite(decay) or not 0.0 <= decay < 1.0:
         raise ValueError(f"--ema_decay must lie in [0, 1) (0: off), got {decay}")
     return decay if decay > 0 else None
+
+
+def groups_arg(args):
+    """--no_decay / --lr_scale as ParamGroups' keywords: None when neither is set (one group, the reference's
+    optimizer), else {"no_decay", "lr_scale": {prefix: multiplier}}.  A malformed PREFIX=MULT is an error."""
+    no_decay = getattr(args, "no_decay", None) or "none"
+    scale = {}
+    for item in getattr(args, "lr_scale", None) or []:
+        prefix, sep, mult = str(item).rpartition("=")
+        try:
+            scale[prefix] = float(mult)
+        except ValueError:
+            sep = ""
+        if not sep or not prefix:
+            raise ValueError(f"--lr_scale takes PREFIX=MULT (e.g. vExtract=0.1), got {item!r}")
+    if no_decay == "none" and not scale:
+        return None
+    return {"no_decay": no_decay, "lr_scale": scale}
 
 
 def check_grad_norm(norm, step):
@@ -470,14 +489,21 @@ class Trainer:
             self.store.refresh_shadow()
         clip = clip_arg(args)
         self.clip = clip is not None
+        gkw = groups_arg(args)      # parameter groups only when a flag asks for them: the plain kernels otherwise
+        self.groups = ParamGroups(model, self.store, args.l2_decacy, **gkw) if gkw is not None else None
         if getattr(args, "optimizer", "sgd") == "adamw":   # src/trainer.py:78
             self.optimizer = FusedAdamW(self.store, args.learning_rate,
                                         betas=(getattr(args, "adam_beta1", 0.9), getattr(args, "adam_beta2", 0.999)),
                                         eps=getattr(args, "adam_eps", 1e-8), weight_decay=args.l2_decacy,
-                                        max_grad_norm=clip)
+                                        max_grad_norm=clip, groups=self.groups)
         else:
             self.optimizer = FusedSGD(self.store, args.learning_rate, momentum=0.9, weight_decay=args.l2_decacy,
-                                      max_grad_norm=clip)
+                                      max_grad_norm=clip, groups=self.groups)
+        if self.groups is not None:
+            rows = self.groups.summary()
+            self.logger(f"parameter groups: {len(rows)} (no_decay {self.groups.no_decay})")
+            for k, (mult, wd, tensors, elems) in enumerate(rows):
+                self.logger(f"  group {k}: lr x {mult:g}, weight decay {wd:g}: {tensors} tensors, {elems} elements")
         steps_per_epoch = max(1, int(len(self.trainloader) / self.accum_step))
         self.scheduler = CosineAnnealingLR(self.optimizer, T_max=self.train_epochs * steps_per_epoch)
         # the weight EMA starts after the rank-0 broadcast above: identical bytes and one deterministic update on

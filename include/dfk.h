@@ -467,6 +467,35 @@ int dfk_adamw_step_runs_clip(float* param, const float* grad, float* exp_avg, fl
                              float eps, float weight_decay, const float* corr, int32_t nclass, float grad_scale,
                              const void* grad_bf16, const float* clip_coef, hipStream_t stream);
 
+/* Parameter groups: a learning-rate multiplier and a weight decay per group of parameters, as the per-group dicts of
+ * torch.optim (the reference builds its optimizer from such a list, with 'initial_lr', at src/trainer.py:80-82; the
+ * Swin recipes exempt norm / bias / position parameters from the decay this way).  The twins of dfk_sgd_step_runs /
+ * dfk_adamw_step_runs (and of their _clip forms): the same run table, alignment and betas / eps rules, and the same
+ * arithmetic per element, with lr and weight_decay looked up per quad of 4 elements instead of passed once:
+ *   group_map:   DEVICE uint8 [map_len], one byte per 8 elements of the store (every parameter starts at a multiple of
+ *                8 elements, so a quad lies in one cell; the <= 7 alignment-padding elements behind a tensor share its
+ *                byte and hold p = g = m = v = 0, which stays 0 under any pair; the elements of a run's n % 4 tail
+ *                take the byte of their own index).  gid = min(byte, ngroups - 1): no value in the map can take a read
+ *                outside group_hyper.
+ *   group_hyper: DEVICE fp32 [ngroups][2] = {lr_mult, weight_decay}, 8-B aligned, 1 <= ngroups <= 256, read at every
+ *                launch: a value changed between two replays of a captured step takes effect without a recapture.
+ *   lr_e = lr * lr_mult[gid] (one rounded fp32 multiply; lr_mult == 1 leaves lr's bits), wd_e = weight_decay[gid].
+ *   SGD: dfk_sgd_step's update with lr_e, wd_e.  AdamW: decay = (float)(1 - (double)lr_e * (double)wd_e),
+ *   step = lr_e * c1, formed per quad.  With a single group {1, wd} the results are the twins' bits.
+ * clip_coef == NULL: no clipping (dfk_*_step_runs' arithmetic); a device pointer: dfk_*_step_runs_clip's.
+ * DFK_EINVAL before any device work: a NULL group_map or group_hyper, group_hyper not 8-B aligned, ngroups outside
+ * 1..256, map_len < ceil(max run end / 8), and the twins' own rules.  DFK_ENOTSUP: nruns > 64 (the caller sends chunks
+ * of 64 runs; there is no one-run variant). */
+int dfk_sgd_step_runs_groups(float* param, const float* grad, float* momentum_buf, void* bf16_shadow,
+                             const int64_t* runs, int32_t nruns, const float* lr_dev, float lr, float momentum,
+                             const uint8_t* group_map, int64_t map_len, const float* group_hyper, int32_t ngroups,
+                             float grad_scale, const void* grad_bf16, const float* clip_coef, hipStream_t stream);
+int dfk_adamw_step_runs_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                               const int64_t* runs, int32_t nruns, const float* lr_dev, float lr, double b1, double b2,
+                               float eps, const float* corr, int32_t nclass, const uint8_t* group_map, int64_t map_len,
+                               const float* group_hyper, int32_t ngroups, float grad_scale, const void* grad_bf16,
+                               const float* clip_coef, hipStream_t stream);
+
 /* Exponential moving average of the weights (csrc/ema.hip): one more flat fp32 buffer `ema` over the parameter
  * store, updated right after the optimizer step, inside the same captured graph, with no host involvement.
  * dfk_ema_prelude, once per step ahead of the update (one workgroup, one thread acts): t = (*num_updates)++ is the

@@ -2,7 +2,7 @@
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
 // conv0, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
 // dims, the SGD and AdamW entry points' buffers / run table / hyper-parameters, the gradient-clipping entry points' slab /
-// coefficient / max_norm / run table, the weight-EMA entry points' buffers / decay), which must return DFK_EINVAL before touching
+// coefficient / max_norm / run table, the parameter-group entry points' map / pairs / group count, the weight-EMA entry points' buffers / decay), which must return DFK_EINVAL before touching
 // the device.  Built and run by tools/asan/run.sh.
 #include <cstdio>
 #include <cstring>
@@ -320,6 +320,77 @@ int main() {
                                     nullptr, fx, nullptr) == DFK_EINVAL);
     EXPECT(dfk_adamw_step_runs_clip(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, 0.f, fx, 1, 1.f,
                                     odd, fx, nullptr) == DFK_EINVAL);      // grad_bf16 not 8-B aligned
+  }
+  {
+    // parameter groups: the *_runs_groups entry points reject a missing / misaligned table, a group count outside
+    // 1..256 and a map shorter than the runs reach, and keep their twins' run-table / alignment / hyper-parameter rules
+    float* fx = reinterpret_cast<float*>(0x10000);
+    float* odd = reinterpret_cast<float*>(0x10004);
+    const uint8_t* gm = reinterpret_cast<const uint8_t*>(0x40001);         // the map needs no alignment
+    int64_t runs[65 * 4];
+    for (int r = 0; r < 65; ++r) { runs[4 * r] = 64 * r; runs[4 * r + 1] = 40; runs[4 * r + 2] = 0; runs[4 * r + 3] = 0; }
+    // two runs end at element 104: 13 map bytes
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, nullptr, 13, fx, 3, 1.f, nullptr,
+                                    nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, gm, 13, nullptr, 3, 1.f, nullptr,
+                                    nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, gm, 13, odd, 3, 1.f, nullptr,
+                                    nullptr, nullptr) == DFK_EINVAL);      // pairs not 8-B aligned
+    for (int32_t bad : {0, -1, 257})
+      EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, gm, 13, fx, bad, 1.f, nullptr,
+                                      nullptr, nullptr) == DFK_EINVAL);
+    for (int64_t bad : {(int64_t)12, (int64_t)0, (int64_t)-1})
+      EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, gm, bad, fx, 3, 1.f, nullptr,
+                                      nullptr, nullptr) == DFK_EINVAL);    // map shorter than ceil(104 / 8)
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 65, fx, 0.f, 0.9f, gm, 1024, fx, 3, 1.f, nullptr,
+                                    nullptr, nullptr) == DFK_ENOTSUP);
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 65, fx, 0.f, 0.9f, gm, 1024, fx, 3, 1.f, nullptr, fx,
+                                    nullptr) == DFK_ENOTSUP);              // with a clip coefficient too
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 0, fx, 0.f, 0.9f, gm, 13, fx, 3, 1.f, nullptr, nullptr,
+                                    nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, nullptr, 2, fx, 0.f, 0.9f, gm, 13, fx, 3, 1.f, nullptr,
+                                    nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_groups(nullptr, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, gm, 13, fx, 3, 1.f, nullptr,
+                                    nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, odd, nullptr, runs, 2, fx, 0.f, 0.9f, gm, 13, fx, 3, 1.f, nullptr, nullptr,
+                                    nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, odd, runs, 2, fx, 0.f, 0.9f, gm, 13, fx, 3, 1.f, nullptr, nullptr,
+                                    nullptr) == DFK_EINVAL);               // shadow not 8-B aligned
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, gm, 13, fx, 3, 1.f, odd, nullptr,
+                                    nullptr) == DFK_EINVAL);               // grad_bf16 not 8-B aligned
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, nullptr, 13,
+                                      fx, 3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 13,
+                                      nullptr, 3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 13,
+                                      odd, 3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    for (int32_t bad : {0, -1, 257})
+      EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 13,
+                                        fx, bad, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 12, fx,
+                                      3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 12, fx,
+                                      3, 1.f, nullptr, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 65, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 1024,
+                                      fx, 3, 1.f, nullptr, nullptr, nullptr) == DFK_ENOTSUP);
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 65, gm, 13, fx,
+                                      3, 1.f, nullptr, nullptr, nullptr) == DFK_ENOTSUP);
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, nullptr, 1, gm, 13,
+                                      fx, 3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);   // no corrections
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 1.0, 0.999, 1e-8f, fx, 1, gm, 13, fx,
+                                      3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);       // b1 = 1
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 0.f, fx, 1, gm, 13, fx, 3,
+                                      1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);          // eps = 0
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, odd, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 13, fx,
+                                      3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    runs[7] = 1;                                                           // class index beyond nclass
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 13, fx,
+                                      3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    runs[7] = 0; runs[4] = 66;                                             // run start not a multiple of 4
+    EXPECT(dfk_adamw_step_runs_groups(fx, fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9, 0.999, 1e-8f, fx, 1, gm, 14, fx,
+                                      3, 1.f, nullptr, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_sgd_step_runs_groups(fx, fx, fx, nullptr, runs, 2, fx, 0.f, 0.9f, gm, 14, fx, 3, 1.f, nullptr, nullptr,
+                                    nullptr) == DFK_EINVAL);
   }
   {
     // weight EMA: the prelude, the update and the swap reject malformed calls; an empty buffer is a no-op

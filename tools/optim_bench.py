@@ -10,7 +10,9 @@ FusedAdamW.step with max_grad_norm on and off.  With --step also the C2 step lev
 SGD and AdamW, each with clipping off and on, and SGD with the weight EMA on), for orientation.  Weight EMA:
 ema_update (dfk_ema_prelude + dfk_ema_update over the whole store: p read, e read and written, 12 B per element, 12/22
 of the yardstick by the bytes model) and ema_swap (dfk_ema_swap: p and e read and written, the shadow written, 18 B
-per element).  With --bits the line also carries a sha256 of every
+per element).  Parameter groups: dfk_sgd_step_runs_groups / dfk_adamw_step_runs_groups over the same run tables with the
+four groups of --no_decay norm_bias and --lr_scale {v,a,pa}Extract=0.1 (one map byte per 8 elements on top of the 22 /
+30 B streams: +0.6 % / +0.4 % by the bytes model), interleaved with their plain twins.  With --bits the line also carries a sha256 of every
 state buffer after the timed calls: the sequence of calls is fixed by reps / inner, the inputs are seeded and no
 kernel uses atomics, so two builds that compute the same thing print the same hashes.  Prints one JSON line.
 Usage: python tools/optim_bench.py [reps] [inner] [--step] [--bits]"""
@@ -25,7 +27,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepfake_amd import kernels as K  # noqa: E402
 from deepfake_amd.models.fused import CONFIGS, build_fused  # noqa: E402
-from deepfake_amd.optim import FusedAdamW, FusedSGD, ParamEMA  # noqa: E402
+from deepfake_amd.optim import FusedAdamW, FusedSGD, ParamEMA, ParamGroups  # noqa: E402
 from deepfake_amd.params import ParamStore  # noqa: E402
 
 HBM_PEAK = 8e12   # bytes / s
@@ -123,6 +125,8 @@ def main():
     def ema_update():
         K.ema_prelude(ema.num_updates, ema.weight, ema.decay, ema.warmup)
         K.ema_update(store.flat, ema.ema, ema.weight)
+    groups = ParamGroups(model, store, 1e-3, no_decay="norm_bias",
+                         lr_scale={"vExtract": 0.1, "aExtract": 0.1, "paExtract": 0.1})
     K.adamw_prelude(adam.counters, adam.corr, [(c, g) for c, g in enumerate(adam.gates)], b1, b2)
     cases = {
         "sgd_step_runs": lambda: K.sgd_step_runs(store.flat, store.grad, sgd.buf, store.shadow, sgd_tab, 0.9, 1e-3,
@@ -130,6 +134,12 @@ def main():
         "adamw_step_runs": lambda: K.adamw_step_runs(store.flat, store.grad, adam.exp_avg, adam.exp_avg_sq,
                                                      store.shadow, adam_tab, b1, b2, adam.eps, 1e-3, adam.lr_dev,
                                                      adam.corr),
+        "sgd_step_runs_groups": lambda: K.sgd_step_runs_groups(store.flat, store.grad, sgd.buf, store.shadow, sgd_tab,
+                                                               0.9, sgd.lr_dev, groups.group_map, groups.group_hyper),
+        "adamw_step_runs_groups": lambda: K.adamw_step_runs_groups(store.flat, store.grad, adam.exp_avg,
+                                                                   adam.exp_avg_sq, store.shadow, adam_tab, b1, b2,
+                                                                   adam.eps, adam.lr_dev, adam.corr, groups.group_map,
+                                                                   groups.group_hyper),
         "FusedAdamW.step": adam.step,
         "grad_norm": grad_norm,
         "FusedSGD.step": sgd.step,
@@ -142,7 +152,8 @@ def main():
     med = {k: statistics.median(v) for k, v in ms.items()}
     bytes_per = {"sgd_step_runs": 22, "adamw_step_runs": 30, "FusedAdamW.step": 30, "grad_norm": 4,
                  "FusedSGD.step": 22, "FusedSGD.step+clip": 26, "FusedAdamW.step+clip": 34, "ema_update": 12,
-                 "ema_swap": 18}
+                 "ema_swap": 18, "sgd_step_runs_groups": 22.125, "adamw_step_runs_groups": 30.125}
+    ratio = {k: [g / p for g, p in zip(ms[k + "_step_runs_groups"], ms[k + "_step_runs"])] for k in ("sgd", "adamw")}
     elems = {k: store.numel if k.startswith("ema_") else n for k in med}   # the EMA kernels cover the gaps too
     out = {"config": "c2", "elements": n, "store_elements": store.numel, "runs": len(runs),
            "classes": len(adam.gates), "reps": reps, "inner": inner,
@@ -161,6 +172,13 @@ def main():
            "ema_update_over_bytes_model": round(med["ema_update"] / (med["sgd_step_runs"] * 12 / 22), 3),
            "ema_swap_over_sgd": round(med["ema_swap"] / med["sgd_step_runs"], 4),
            "ema_swap_over_bytes_model": round(med["ema_swap"] / (med["sgd_step_runs"] * 18 / 22), 3),
+           "groups": [{"lr_scale": m, "weight_decay": w, "tensors": t, "elements": e}
+                      for m, w, t, e in groups.summary()],
+           # groups kernel / plain twin: of the medians, and median / min / max of the per-repeat ratios (the spread)
+           "groups_over_plain": {k: {"of_medians": round(med[k + "_step_runs_groups"] / med[k + "_step_runs"], 4),
+                                     "median": round(statistics.median(v), 4), "min": round(min(v), 4),
+                                     "max": round(max(v), 4)} for k, v in ratio.items()},
+           "groups_bytes_ratio": {"sgd": round(22.125 / 22, 4), "adamw": round(30.125 / 30, 4)},
            "ema_num_updates": int(ema.num_updates),
            "grad_norm_value": [round(v, 6) for v in adam_c.grad_norm.tolist()],
            "device": torch.cuda.get_device_name(0)}
