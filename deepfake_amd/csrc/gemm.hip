@@ -1,20 +1,22 @@
 // Generic MFMA GEMM for gfx950 with operand views (plain / k-major / implicit
 // conv), batching, split-K and fused epilogues.  See include/dfk.h.
 //
-// Tile 128x128 (or 64x64 for grids too small to fill the chip) per 256-thread workgroup (4 waves, 2x2).
 //   bf16: v_mfma_f32_16x16x32_bf16, BK = 64 (2 MFMA k-steps per staged tile)
 //   f32 : v_mfma_f32_16x16x4_f32   (exact fp32, parity mode), BK = 32
-// Staging: global -> registers (16-B vectors along each view's contiguous dim)
-// -> LDS in the view's NATURAL orientation:
-//   k-contiguous operand  -> tile [row][k]  : fragments by ds_read_b128
-//   k-major operand       -> tile [k][row]  : bf16 fragments by two
-//                            ds_read_b64_tr_b16 (hardware transpose), so the
-//                            dX / dW GEMMs of every Linear never scatter.
-// LDS is double-buffered: the next tile's global loads are in flight during
-// the current tile's MFMAs, one barrier per k-tile.
-// bf16 launches with plain views take the LDS-DMA kernel instead (gemm_dma_kernel, below): the same tiles
-// and MFMAs, operands moved HBM -> LDS by buffer_load ... lds with source-swizzled, conflict-free images.
-// The register-staged kernel remains for fp32 parity mode and the implicit-conv views.
+// Two kernels, chosen by dma_vec() / pick_tile() below:
+//   gemm_dma_kernel (bf16, 16-B aligned views below 2 GB): operands move HBM -> LDS by buffer_load ... lds
+//     into source-swizzled, conflict-free images, 2 LDS stages.  Workgroup tiles: 128x128 (2x2 waves of
+//     64x64) for large grids and the weight gradients, 64x64 (2x2 waves of 32x32) for small grids, and for
+//     small forward / dX grids the 8-wave 128x64 / 64x128 (4x2 / 2x4 waves of 32x32).
+//   gemm_kernel (fp32 parity mode, unaligned or odd extents, views of 2 GB and more): register-staged,
+//     128x128 or 64x64 tiles per 256-thread workgroup.  Staging: global -> registers (16-B vectors along
+//     each view's contiguous dim) -> LDS in the view's NATURAL orientation:
+//       k-contiguous operand  -> tile [row][k]  : fragments by ds_read_b128
+//       k-major operand       -> tile [k][row]  : bf16 fragments by two
+//                                ds_read_b64_tr_b16 (hardware transpose), so the
+//                                dX / dW GEMMs of every Linear never scatter.
+//     LDS is double-buffered: the next tile's global loads are in flight during
+//     the current tile's MFMAs, one barrier per k-tile.
 #include <mutex>
 
 #include "common.h"
@@ -296,10 +298,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const dfk_gemm_args g, int kc
   // register ring of PF staged k-tiles in flight (loads are unconditional: past kend they are masked
   // to zero by the view bounds), LDS double buffer: tile t is computed from LDS[t&1] while tile t+1
   // moves from its registers into LDS[(t+1)&1] and tile t+1+PF is requested into the freed registers.
-#ifndef DFK_GEMM_PF64
-#define DFK_GEMM_PF64 1
-#endif
-  constexpr int PF = WT == 32 ? 4 : DFK_GEMM_PF64;
+  constexpr int PF = WT == 32 ? 4 : 1;
   uint4 ra[PF][VA], rb[PF][VB];
   const int ntile = kend > kbeg ? (kend - kbeg + TBK - 1) / TBK : 0;
 #pragma unroll
@@ -531,22 +530,18 @@ __device__ __forceinline__ void tile_epilogue(const dfk_gemm_args& g, float* sme
 //                         -> the ds_read_b64_tr_b16 transposed reads are conflict-free
 // (screened against the LDS lane-group/bank model of the microarchitecture guide).  Out-of-range chunks
 // (rows past M/N, k past the split's end) get a voffset past the descriptor's range: the hardware
-// returns zeros, so the loop has no branches around loads.  S LDS stages: tile t+S-1 is requested
-// right after the barrier that retires tile t, one raw s_barrier per k-tile, counted vmcnt waits
-// (an LDS-DMA is a VM-counter load; __syncthreads() would drain it with vmcnt(0)).
+// returns zeros, so the loop has no branches around loads.  Two LDS stages: tile t+1 is requested
+// right after the barrier that retires tile t, one raw s_barrier per k-tile (an LDS-DMA is a VM-counter
+// load, waited for with vmcnt(0) before that barrier).  Deeper rings measured slower at every tile shape:
+// occupancy hides the DMA latency better (C2 sweep; 128x128: 69 KB -> two workgroups per CU; dW with 3
+// stages 116 -> 119 us, C2 256.8 -> 247.7 clips/s, profiles/gemm/r4sdw_*).
 typedef __attribute__((address_space(3))) void lds_void;
+constexpr int kStages = 2;   // LDS ring depth of the LDS-DMA kernels (bf16 and MX)
 
 template <int ROWS>
 __device__ __forceinline__ int kmaj_swz(int k) {   // 16-B chunk XOR of k-row k in a [64][ROWS] bf16 image
-  // (ROWS = 256: a k-row spans two bank rows; the XOR stays below 16, the same bank pattern as 128)
   if constexpr (ROWS >= 128) return ((k & 3) | ((k >> 1) & 4)) << 1;
   else return (((k >> 1) & 1) | ((k >> 2) & 2)) << 1;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
 }
 
 // One operand's DMA for k-tile k0: NI wave-instructions per wave, each 64 lanes x 16 B into 1 KB of the
@@ -614,23 +609,21 @@ __host__ __device__ __forceinline__ long view_extent(const dfk_view& v, long row
   return ((rows - 1) * v.ld + cols) * 2;
 }
 
-// Workgroup tile (NWM * 64/... ) = BM x BN from NWM x NWN waves of WT x WT each: 64x64 (2x2 waves of 32),
-// 128x128 (2x2 waves of 64) and 256x128 (4x2 waves of 64, 512 threads: twice the MFMA work per k-tile for
-// 1.5x the staged bytes, so one DMA in flight covers more of its latency).
+// Workgroup tile BM x BN from NWM x NWN waves of WT x WT each: 64x64 and 128x128 (2x2 waves of 32 / 64),
+// 128x64 and 64x128 (4x2 / 2x4 waves of 32).
 // splits from which a dW's fused bias gradient goes through per-split partials + rowsum_reduce_kernel instead of
 // atomics (the same-address atomics serialise only when many splits add; below this, one more launch costs more)
 constexpr int kRsPartialMin = 32;
 
 // The kernel body for workgroup `bid` of a `grid`-shaped launch: gemm_dma_kernel passes blockIdx / gridDim, the
 // grouped weight-gradient kernel (below) the coordinates it decoded for one of its problems.
-template <int WT, int NWM, int NWN, bool AK, bool BKM, int S, bool RS, bool CONV>
+template <int WT, int NWM, int NWN, bool AK, bool BKM, bool RS, bool CONV>
 __device__ __forceinline__ void gemm_dma_body(const dfk_gemm_args& g, int kchunk, int evec, SplitK sk, const dim3 bid,
                                               const dim3 grid) {
-  constexpr int NWV = NWM * NWN, BM = NWM * WT, BN = NWN * WT, MI = WT / 16, BK = 64;
+  constexpr int NWV = NWM * NWN, BM = NWM * WT, BN = NWN * WT, MI = WT / 16, BK = 64, S = kStages;
   constexpr int STAGE = (BM + BN) * BK;                         // elements per LDS stage
   constexpr int ES = WT + 4;
   constexpr int SMEM = S * STAGE * 2 > NWV * WT * ES * 4 ? S * STAGE * 2 : NWV * WT * ES * 4;   // bytes
-  constexpr int LPT = Dma<AK, BM, NWV, CONV>::NI + Dma<BKM, BN, NWV, CONV>::NI;   // DMA instructions per wave per tile
   __shared__ __attribute__((aligned(16))) float smem_f[SMEM / 4];   // the ONE LDS object (staging + epilogue)
   bf16raw* smem = reinterpret_cast<bf16raw*>(smem_f);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -688,20 +681,15 @@ __device__ __forceinline__ void gemm_dma_body(const dfk_gemm_args& g, int kchunk
 #pragma unroll
   for (int i = 0; i < MH; ++i) accr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // (spelled as the ring's fill loop: as a plain `if (ntile > 0) issue(kbeg, smem)` the compiler schedules the
+  // prologue differently)
 #pragma unroll
   for (int d = 0; d < S - 1; ++d)
     if (d < ntile) {
       issue(kbeg + d * BK, smem + d * STAGE);
     }
   for (int t = 0; t < ntile; ++t) {
-    // retire tile t: S-2 later tiles may stay in flight (fewer near the end)
-    if constexpr (S == 4) {
-      if (t + 2 < ntile) wait_vm<2 * LPT>(); else if (t + 1 < ntile) wait_vm<LPT>(); else wait_vm<0>();
-    } else if constexpr (S == 3) {
-      if (t + 1 < ntile) wait_vm<LPT>(); else wait_vm<0>();
-    } else {
-      wait_vm<0>();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // retire tile t
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of tile t-1 are complete
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -764,10 +752,10 @@ __device__ __forceinline__ void gemm_dma_body(const dfk_gemm_args& g, int kchunk
                              (z * (int)grid.y + tmi) * (int)grid.x + tn, evec, sk);
 }
 
-template <int WT, int NWM, int NWN, bool AK, bool BKM, int S, bool RS, bool CONV = false>
+template <int WT, int NWM, int NWN, bool AK, bool BKM, bool RS, bool CONV>
 __global__ __launch_bounds__(NWM * NWN * 64) void gemm_dma_kernel(const dfk_gemm_args g, int kchunk, int evec,
                                                                   SplitK sk) {
-  gemm_dma_body<WT, NWM, NWN, AK, BKM, S, RS, CONV>(g, kchunk, evec, sk, blockIdx, gridDim);
+  gemm_dma_body<WT, NWM, NWN, AK, BKM, RS, CONV>(g, kchunk, evec, sk, blockIdx, gridDim);
 }
 
 // Grouped weight gradients (dfk_gemm_dw_group): up to kDwGroupMax independent dW problems of one tile shape in one
@@ -821,7 +809,7 @@ __global__ __launch_bounds__(256) void gemm_dw_group_kernel(const DwGroup T) {
   g.rowsum = P.rowsum;
   const int xy = gx * gy;
   const dim3 bid(local % gx, (local % xy) / gx, local / xy), grid(gx, gy, gz);
-  gemm_dma_body<WT, 2, 2, true, true, 2, RS, false>(g, P.kchunk, 0, SplitK{nullptr, nullptr}, bid, grid);
+  gemm_dma_body<WT, 2, 2, true, true, RS, false>(g, P.kchunk, 0, SplitK{nullptr, nullptr}, bid, grid);
 }
 
 // rowsum[row] += sum over splits of part[split][row] (the bias gradient of an atomic split-K dW, fixed order):
@@ -925,158 +913,129 @@ bool view_vec(const dfk_view& v, int vec) {
   return true;
 }
 
-template <typename T, int WT, bool VECOK, bool CONV>
-void dispatch_wt(const dfk_gemm_args& g, dim3 grid, int kchunk, int evec, SplitK sk, hipStream_t s) {
-  if (g.a_kmajor) {
-    if (g.b_kmajor) {
-      if (g.rowsum) hipLaunchKernelGGL((gemm_kernel<T, WT, true, true, VECOK, CONV, true>), grid, dim3(NT), 0, s, g, kchunk, evec, sk);
-      else hipLaunchKernelGGL((gemm_kernel<T, WT, true, true, VECOK, CONV>), grid, dim3(NT), 0, s, g, kchunk, evec, sk);
-    }
-    else hipLaunchKernelGGL((gemm_kernel<T, WT, true, false, VECOK, CONV>), grid, dim3(NT), 0, s, g, kchunk, evec, sk);
-  } else {
-    if (g.b_kmajor) hipLaunchKernelGGL((gemm_kernel<T, WT, false, true, VECOK, CONV>), grid, dim3(NT), 0, s, g, kchunk, evec, sk);
-    else hipLaunchKernelGGL((gemm_kernel<T, WT, false, false, VECOK, CONV>), grid, dim3(NT), 0, s, g, kchunk, evec, sk);
-  }
-}
-
-// implicit-conv views (wav2vec2 conv1-6 and their weight gradients): 2 LDS stages, 64x64 / 128x128 tiles
-template <int WT>
-void dispatch_dma_conv(const dfk_gemm_args& g, dim3 grid, int kchunk, int evec, SplitK sk, hipStream_t s) {
-  const dim3 blk(256);
-  if (g.a_kmajor) {
-    if (g.b_kmajor) {
-      if (g.rowsum) hipLaunchKernelGGL((gemm_dma_kernel<WT, 2, 2, true, true, 2, true, true>), grid, blk, 0, s, g, kchunk, evec, sk);
-      else hipLaunchKernelGGL((gemm_dma_kernel<WT, 2, 2, true, true, 2, false, true>), grid, blk, 0, s, g, kchunk, evec, sk);
-    }
-    else hipLaunchKernelGGL((gemm_dma_kernel<WT, 2, 2, true, false, 2, false, true>), grid, blk, 0, s, g, kchunk, evec, sk);
-  } else {
-    if (g.b_kmajor) hipLaunchKernelGGL((gemm_dma_kernel<WT, 2, 2, false, true, 2, false, true>), grid, blk, 0, s, g, kchunk, evec, sk);
-    else hipLaunchKernelGGL((gemm_dma_kernel<WT, 2, 2, false, false, 2, false, true>), grid, blk, 0, s, g, kchunk, evec, sk);
-  }
-}
-
-template <int WT, int NWM, int NWN, int S>
-void dispatch_dma_s(const dfk_gemm_args& g, dim3 grid, int kchunk, int evec, SplitK sk, hipStream_t s) {
-  const dim3 blk(NWM * NWN * 64);
-  if (g.a_kmajor) {
-    if (g.b_kmajor) {
-      if (g.rowsum) hipLaunchKernelGGL((gemm_dma_kernel<WT, NWM, NWN, true, true, S, true>), grid, blk, 0, s, g, kchunk, evec, sk);
-      else hipLaunchKernelGGL((gemm_dma_kernel<WT, NWM, NWN, true, true, S, false>), grid, blk, 0, s, g, kchunk, evec, sk);
-    }
-    else hipLaunchKernelGGL((gemm_dma_kernel<WT, NWM, NWN, true, false, S, false>), grid, blk, 0, s, g, kchunk, evec, sk);
-  } else {
-    if (g.b_kmajor) hipLaunchKernelGGL((gemm_dma_kernel<WT, NWM, NWN, false, true, S, false>), grid, blk, 0, s, g, kchunk, evec, sk);
-    else hipLaunchKernelGGL((gemm_dma_kernel<WT, NWM, NWN, false, false, S, false>), grid, blk, 0, s, g, kchunk, evec, sk);
-  }
-}
-
-// LDS-DMA kernel stages (tuning runs may override): 2 for both tile sizes (C2 sweep: occupancy hides the
-// DMA latency better than a deeper ring; 128x128: 69 KB -> two workgroups per CU)
-int dma_stages(int wt) {
-  static const int s128 = getenv("DFK_DMA_S128") ? atoi(getenv("DFK_DMA_S128")) : 2;
-  if (wt == 128) return s128;
-  static const int s64 = getenv("DFK_DMA_S64") ? atoi(getenv("DFK_DMA_S64")) : 2;
-  static const int s32 = getenv("DFK_DMA_S32") ? atoi(getenv("DFK_DMA_S32")) : 2;
-  return wt == 64 ? s64 : s32;
-}
-
-// ring depth of the weight gradients' (k-major A) 128x128 (wt 64) and 64x64 (wt 32) tiles
-int dw_stages(int wt) {
-  static const int sdw = getenv("DFK_DMA_SDW") ? atoi(getenv("DFK_DMA_SDW")) : 2;
-  static const int sdw32 = getenv("DFK_DMA_SDW32") ? atoi(getenv("DFK_DMA_SDW32")) : 2;   // their 64x64 tiles (A/B)
-  return wt == 64 ? sdw : sdw32;
-}
-
-// wt: 32 -> 64x64 tiles, 64 -> 128x128, 128 -> 256x128 (8 waves)
-void dispatch_dma(const dfk_gemm_args& g, int wt, dim3 grid, int kchunk, int evec, SplitK sk, hipStream_t s) {
-  if (g.a.conv_cg > 0 || g.b.conv_cg > 0) {
-    if (wt == 32) dispatch_dma_conv<32>(g, grid, kchunk, evec, sk, s);
-    else dispatch_dma_conv<64>(g, grid, kchunk, evec, sk, s);
-    return;
-  }
-  // weight gradients (k-major A: the token dimension is the reduction) on 128x128 tiles: tuning knob for their ring
-  // depth (3 stages measured slower: dW 116 -> 119 us, C2 256.8 -> 247.7 clips/s, profiles/gemm/r4sdw_*)
-  const int st = g.a_kmajor && (wt == 64 || wt == 32) ? dw_stages(wt) : dma_stages(wt);
-  static const int s8w = getenv("DFK_DMA_S8W") ? atoi(getenv("DFK_DMA_S8W")) : 2;   // A/B: ring depth of the 8-wave tiles
-  if (wt == 33) {   // 128 x 64 (8 waves of 32 x 32)
-    if (s8w == 3) dispatch_dma_s<32, 4, 2, 3>(g, grid, kchunk, evec, sk, s);
-    else dispatch_dma_s<32, 4, 2, 2>(g, grid, kchunk, evec, sk, s);
-    return;
-  }
-  if (wt == 34) {   // 64 x 128
-    if (s8w == 3) dispatch_dma_s<32, 2, 4, 3>(g, grid, kchunk, evec, sk, s);
-    else dispatch_dma_s<32, 2, 4, 2>(g, grid, kchunk, evec, sk, s);
-    return;
-  }
-  if (wt == 128) {
-    if (st == 3) dispatch_dma_s<64, 4, 2, 3>(g, grid, kchunk, evec, sk, s);
-    else dispatch_dma_s<64, 4, 2, 2>(g, grid, kchunk, evec, sk, s);
-  } else if (wt == 64) {
-    if (st == 2) dispatch_dma_s<64, 2, 2, 2>(g, grid, kchunk, evec, sk, s);
-    else if (st == 4) dispatch_dma_s<64, 2, 2, 4>(g, grid, kchunk, evec, sk, s);
-    else dispatch_dma_s<64, 2, 2, 3>(g, grid, kchunk, evec, sk, s);
-  } else {
-    if (st == 2) dispatch_dma_s<32, 2, 2, 2>(g, grid, kchunk, evec, sk, s);
-    else if (st == 4) dispatch_dma_s<32, 2, 2, 4>(g, grid, kchunk, evec, sk, s);
-    else dispatch_dma_s<32, 2, 2, 3>(g, grid, kchunk, evec, sk, s);
-  }
+// whole 16-B vectors along both operands' contiguous dims (else tails load element-wise)
+bool views_vec(const dfk_gemm_args& g, int vec) {
+  return view_vec(g.a, vec) && view_vec(g.b, vec) && (g.a_kmajor ? g.M : g.K) % vec == 0 &&
+         (g.b_kmajor ? g.N : g.K) % vec == 0;
 }
 
 // the LDS-DMA kernel addresses each operand through a buffer descriptor with 32-bit byte offsets
 bool dma_ok(const dfk_gemm_args& g) {
-  static const int off = getenv("DFK_GEMM_DMA") ? atoi(getenv("DFK_GEMM_DMA")) == 0 : 0;   // A/B runs only
-  if (off || g.dtype != DFK_BF16) return false;
+  if (g.dtype != DFK_BF16) return false;
   const long ea = g.a_kmajor ? view_extent(g.a, g.K, g.M) : view_extent(g.a, g.M, g.K);
   const long eb = g.b_kmajor ? view_extent(g.b, g.K, g.N) : view_extent(g.b, g.N, g.K);
   return ea < 0x7fffffffL && eb < 0x7fffffffL;
 }
 
-template <typename T, bool VECOK, bool CONV>
-void dispatch(const dfk_gemm_args& g, int wt, dim3 grid, int kchunk, int evec, SplitK sk, hipStream_t s) {
-  if (wt == 32) dispatch_wt<T, 32, VECOK, CONV>(g, grid, kchunk, evec, sk, s);
-  else dispatch_wt<T, 64, VECOK, CONV>(g, grid, kchunk, evec, sk, s);
-}
+// g runs on gemm_dma_kernel (the LDS-DMA vector path); only that kernel writes bias-gradient partials, so the
+// launch, the workspace size and the grouped-dW plan all ask here
+bool dma_vec(const dfk_gemm_args& g) { return dma_ok(g) && views_vec(g, 8); }
 
-// wave tile: 64 (128 x 128 workgroup tiles) unless that grid has fewer than eight tiles per CU: then 32
-// (64 x 64 tiles, four times the workgroups, half the LDS, a 4-deep register ring of k-tiles in flight)
+// Workgroup tile: nwm x nwn waves of wt x wt
+struct TileShape {
+  int wt, nwm, nwn;
+  int bm() const { return nwm * wt; }
+  int bn() const { return nwn * wt; }
+};
+constexpr TileShape k64x64{32, 2, 2}, k128x128{64, 2, 2}, k128x64{32, 4, 2}, k64x128{32, 2, 4};
+
+// 128x128 tiles from this many of them, else 64x64 (four times the workgroups, half the LDS).  Register-staged
+// kernel, measured on the C2 Linear shapes (tools/gemm_bench.py, both tile shapes): below 2048 128x128 tiles (eight
+// per CU) the 64x64 tiles with the 4-deep k-tile ring win or tie at every K (e.g. [25088,1536]x[1536,384] 98 -> 73
+// us, [6272,3072]x[3072,768] 86 -> 77 us), above it the 128x128 tiles win.  LDS-DMA kernel: from 1024 (C2 sweep:
+// [6272,768]x[768,3072] 74 -> 58 us, the M ~ 1.6k wav2vec2 / SwinV2-stage-3 shapes stay faster on 64x64 tiles)
+constexpr long kTiles128Min = 2048, kTiles128MinDma = 1024;
+
+// wave tile of the 4-wave workgroups: 64 (128x128) or 32 (64x64)
 int pick_wt(const dfk_gemm_args& g) {
-  // caller-planned split-K grids (weight gradients): 128x128 tiles (A/B knob DFK_DW_WT=32: 64x64 tiles, whose
-  // smaller LDS stages let three workgroups per CU keep more bytes in flight)
-  static const int dw_wt = getenv("DFK_DW_WT") ? atoi(getenv("DFK_DW_WT")) : 64;
-  if (g.atomic || g.splitk > 1) return dw_wt == 32 ? 32 : 64;
-  static const int force = getenv("DFK_GEMM_WT") ? atoi(getenv("DFK_GEMM_WT")) : 0;   // tuning runs only
-  if (force == 32 || force == 64) return force;
-  // measured on the C2 Linear shapes (tools/gemm_bench.py, both tile shapes): below 2048 128x128 tiles (eight
-  // per CU) the 64x64 tiles with the k-tile ring win or tie at every K (e.g. [25088,1536]x[1536,384] 98 -> 73
-  // us, [6272,3072]x[3072,768] 86 -> 77 us), above it the 128x128 tiles win
+  // caller-planned split-K grids (weight gradients): 128x128 (64x64 tiles, whose smaller LDS stages let more
+  // workgroups per CU keep bytes in flight, won isolated and lost 1.0 % in the step:
+  // profiles/gemm/r6o_dw_64tiles_step_rejected.txt)
+  if (g.atomic || g.splitk > 1) return 64;
   const long tiles128 = (long)dfk_cdiv(g.N, 128) * dfk_cdiv(g.M, 128) * g.nz0 * g.nz1;
-  // LDS-DMA kernel (below): 128x128 tiles from 1024 of them (C2 sweep: [6272,768]x[768,3072] 74 -> 58 us,
-  // the M ~ 1.6k wav2vec2 / SwinV2-stage-3 shapes stay faster on 64x64 tiles)
-  if (dma_ok(g)) return tiles128 < 1024 ? 32 : 64;
-  return tiles128 < 2048 ? 32 : 64;
+  return tiles128 < (dma_ok(g) ? kTiles128MinDma : kTiles128Min) ? 32 : 64;
 }
 
-// automatic K split for grids that cannot fill the chip (caller asked for no split, no atomics)
-template <typename T>
+TileShape pick_tile(const dfk_gemm_args& g) {
+  const TileShape sq = pick_wt(g) == 64 ? k128x128 : k64x64;
+  if (g.a.conv_cg > 0 || g.b.conv_cg > 0) return sq;   // implicit-conv views (wav2vec2 conv1-6 and their dW)
+  if (g.a_kmajor) return sq;   // dW (the token dimension is the reduction): their fp32 epilogue lost on 8 waves
+  // small grids, forward and dX on the LDS-DMA kernel: 8-wave 128x64 / 64x128 workgroups of 32x32 waves, the longer
+  // side along the larger of M / N (each staged tile feeds twice the MFMA work of a 4-wave 64x64 one; r4u: C2
+  // 247.1 -> 250.6 clips/s, vst4.fc1 dX 69 -> 49 us)
+  if (sq.wt == 32 && dma_vec(g)) return g.M >= g.N ? k128x64 : k64x128;
+  return sq;   // large grids; small ones on the register-staged kernel
+}
+
+// automatic K split for grids that cannot fill the chip (caller asked for no split, no atomics): up to
+// kSplitTarget workgroups (384-1536 within the step's run-to-run spread, no split loses 1.4 %:
+// profiles/gemm/r6q_gemm_split_target_sweep.txt)
+constexpr int kSplitTarget = 768;
+// at least this many k-tiles per split: below that the fp32 slab round trip and the reduce launch cost more than
+// the shorter k-loop saves (C2 sweep of the LDS-DMA kernel: K = 512-2048 run fastest unsplit, K >= 2304 with 3-4
+// splits)
+constexpr int kSplitMinTiles = 12;
 int auto_splitk(const dfk_gemm_args& g) {
-  constexpr int TBK = GT<T>::BK;
   if (g.atomic || g.splitk != 1 || g.M <= 0 || g.N <= 0) return 1;
   const int wt = pick_wt(g);
   const long tiles = (long)dfk_cdiv(g.N, 2 * wt) * dfk_cdiv(g.M, 2 * wt) * g.nz0 * g.nz1;
   if (tiles >= 384) return 1;
-  static const int nosplit = getenv("DFK_GEMM_NOSPLIT") ? atoi(getenv("DFK_GEMM_NOSPLIT")) : 0;   // tuning runs only
-  if (nosplit) return 1;
-  // at least 12 k-tiles per split: below that the fp32 slab round trip and the reduce launch cost more than
-  // the shorter k-loop saves (C2 sweep of the LDS-DMA kernel: K = 512-2048 run fastest unsplit, K >= 2304
-  // with 3-4 splits)
-  const int maxs = g.K / (12 * TBK);
-  static const int target = getenv("DFK_GEMM_SPLIT_TARGET") ? atoi(getenv("DFK_GEMM_SPLIT_TARGET")) : 768;   // tuning runs only
-  const int want = (int)dfk_cdiv(target, tiles);
+  const int maxs = g.K / (kSplitMinTiles * (g.dtype == DFK_BF16 ? GT<bf16raw>::BK : GT<float>::BK));
+  const int want = (int)dfk_cdiv(kSplitTarget, tiles);
   return std::max(1, std::min(maxs, want));
+}
+
+// Every GEMM kernel has one signature; a kernel family maps an operand layout (k-major A, k-major B, fused row
+// sums: k-major x k-major only) to its instantiation, and by_layout() is the one switch over the layouts.
+using GemmKernel = void (*)(const dfk_gemm_args, int, int, SplitK);
+
+template <typename T, int WT, bool VECOK, bool CONV>
+struct RegStaged {
+  template <bool AK, bool BKM, bool RS>
+  static GemmKernel kernel() { return gemm_kernel<T, WT, AK, BKM, VECOK, CONV, RS>; }
+};
+
+template <int WT, int NWM, int NWN, bool CONV>
+struct LdsDma {
+  template <bool AK, bool BKM, bool RS>
+  static GemmKernel kernel() {
+    if constexpr (AK && NWM * NWN == 8) return nullptr;   // pick_tile(): no 8-wave tile takes a k-major A
+    else return gemm_dma_kernel<WT, NWM, NWN, AK, BKM, RS, CONV>;
+  }
+};
+
+template <typename F>
+GemmKernel by_layout(const dfk_gemm_args& g) {
+  if (g.a_kmajor) {
+    if (g.b_kmajor) return g.rowsum ? F::template kernel<true, true, true>() : F::template kernel<true, true, false>();
+    return F::template kernel<true, false, false>();
+  }
+  return g.b_kmajor ? F::template kernel<false, true, false>() : F::template kernel<false, false, false>();
+}
+
+template <typename T>
+GemmKernel pick_kernel(const dfk_gemm_args& g, TileShape t, bool dma, bool vec) {
+  const bool conv = g.a.conv_cg > 0 || g.b.conv_cg > 0, w64 = t.wt == 64;
+  if (dma) {
+    if (t.nwm == 4) return by_layout<LdsDma<32, 4, 2, false>>(g);
+    if (t.nwn == 4) return by_layout<LdsDma<32, 2, 4, false>>(g);
+    if (conv) return w64 ? by_layout<LdsDma<64, 2, 2, true>>(g) : by_layout<LdsDma<32, 2, 2, true>>(g);
+    return w64 ? by_layout<LdsDma<64, 2, 2, false>>(g) : by_layout<LdsDma<32, 2, 2, false>>(g);
+  }
+  if (!vec) return w64 ? by_layout<RegStaged<T, 64, false, true>>(g) : by_layout<RegStaged<T, 32, false, true>>(g);
+  if (conv) return w64 ? by_layout<RegStaged<T, 64, true, true>>(g) : by_layout<RegStaged<T, 32, true, true>>(g);
+  return w64 ? by_layout<RegStaged<T, 64, true, false>>(g) : by_layout<RegStaged<T, 32, true, false>>(g);
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// epilogue 16-B path legal for g (8-element groups of C / residual / aux / bias rows stay 16-B aligned)
+bool epi_vec(const dfk_gemm_args& g) {
+  return !g.c_f32 && aligned16(g.c) && g.ldc % 8 == 0 && g.cbs0 % 8 == 0 && g.cbs1 % 8 == 0 &&
+         (!g.bias || (aligned16(g.bias) && g.bias_bs1 % 8 == 0)) &&
+         (!g.residual || (aligned16(g.residual) && g.ldr % 8 == 0 && g.rbs0 % 8 == 0 && g.rbs1 % 8 == 0)) &&
+         (!g.aux || (aligned16(g.aux) && g.ldaux % 8 == 0));
+}
 
 template <typename T>
 int launch(const dfk_gemm_args& g, hipStream_t s) {
@@ -1099,51 +1058,22 @@ int launch(const dfk_gemm_args& g, hipStream_t s) {
   }
   // split-K through fp32 slabs + a reduce/epilogue kernel: caller-chosen (splitk > 1, no atomics) or
   // automatic for grids too small to fill the chip
-  const int autos = g.splitk > 1 && !g.atomic ? g.splitk : (g.ws ? auto_splitk<T>(g) : 1);
+  const int autos = g.splitk > 1 && !g.atomic ? g.splitk : (g.ws ? auto_splitk(g) : 1);
   dfk_gemm_args gg = g;
   if (autos > 1) gg.splitk = autos;
   int kchunk = dfk_cdiv(g.K, gg.splitk);
   kchunk = dfk_cdiv(kchunk, TBK) * TBK;
-  int wt = pick_wt(g);
-  const bool dma = sizeof(T) == 2 && dma_ok(g);
-  const bool conv = g.a.conv_cg > 0 || g.b.conv_cg > 0;
-  // vector path also needs the contiguous extents to be whole vectors (else tails load element-wise)
-  const bool vec = view_vec(g.a, VEC) && view_vec(g.b, VEC) && (g.a_kmajor ? g.M : g.K) % VEC == 0 &&
-                   (g.b_kmajor ? g.N : g.K) % VEC == 0;
-  if (dma && vec && wt == 64 && !conv) {   // 256x128 tiles (8 waves) when the grid still covers the chip (tuning knob for now)
-    static const long t256 = getenv("DFK_GEMM_T256") ? atol(getenv("DFK_GEMM_T256")) : (1L << 40);
-    const long tiles256 = (long)dfk_cdiv(g.N, 128) * dfk_cdiv(g.M, 256) * g.nz0 * g.nz1 * gg.splitk;
-    if (tiles256 >= t256) wt = 128;
-  }
-  if (dma && vec && wt == 32 && !conv) {
-    // small grids, forward and dX: 8-wave 128x64 / 64x128 workgroups of 32x32 waves, the longer side along the
-    // larger of M / N (each staged tile feeds twice the MFMA work of a 4-wave 64x64 one; r4u: C2 247.1 -> 250.6
-    // clips/s, vst4.fc1 dX 69 -> 49 us); the dW GEMMs (k-major A) keep 64x64 (their fp32 epilogue lost there)
-    static const int t32x = getenv("DFK_GEMM_T32X") ? atoi(getenv("DFK_GEMM_T32X")) : -1;   // A/B: 0 / 1 / 2
-    if (t32x == 1 || (t32x < 0 && !g.a_kmajor && g.M >= g.N)) wt = 33;
-    else if (t32x == 2 || (t32x < 0 && !g.a_kmajor)) wt = 34;
-  }
-  const int bm = wt == 128 ? 256 : (wt == 33 ? 128 : (wt == 34 ? 64 : 2 * wt));
-  const int bn = wt == 128 ? 128 : (wt == 33 ? 64 : (wt == 34 ? 128 : 2 * wt));
-  dim3 grid(dfk_cdiv(g.N, bn), dfk_cdiv(g.M, bm), g.nz0 * g.nz1 * gg.splitk);
+  const bool dma = dma_vec(g), vec = views_vec(g, VEC);
+  const TileShape tile = pick_tile(g);
+  const dim3 grid(dfk_cdiv(g.N, tile.bn()), dfk_cdiv(g.M, tile.bm()), g.nz0 * g.nz1 * gg.splitk);
   if (grid.y > 65535 || grid.z > 65535) return DFK_EINVAL;
-  // epilogue 16-B path: 8-element groups of C / residual / aux / bias rows stay 16-B aligned
-  const bool evec = !g.c_f32 && aligned16(g.c) && g.ldc % 8 == 0 && g.cbs0 % 8 == 0 && g.cbs1 % 8 == 0 &&
-                    (!g.bias || (aligned16(g.bias) && g.bias_bs1 % 8 == 0)) &&
-                    (!g.residual || (aligned16(g.residual) && g.ldr % 8 == 0 && g.rbs0 % 8 == 0 && g.rbs1 % 8 == 0)) &&
-                    (!g.aux || (aligned16(g.aux) && g.ldaux % 8 == 0));
+  const bool evec = epi_vec(g);
   float* slab = autos > 1 ? reinterpret_cast<float*>(g.ws) : nullptr;
   const SplitK sk{slab, slab ? dfk_ticket_slice((long)grid.x * grid.y * g.nz0 * g.nz1, s) : nullptr};
-  if (vec) {
-    if (dma) dispatch_dma(gg, wt, grid, kchunk, evec, sk, s);
-    else if (conv) dispatch<T, true, true>(gg, wt, grid, kchunk, evec, sk, s);
-    else dispatch<T, true, false>(gg, wt, grid, kchunk, evec, sk, s);
-  } else {
-    dispatch<T, false, true>(gg, wt, grid, kchunk, evec, sk, s);
-  }
-  // the bias-gradient partials (after the slab, if any): only gemm_dma_kernel writes them (dma && vec); the
-  // register-staged kernels add the bias gradient atomically into rowsum and leave the workspace untouched
-  if (dma && vec && g.rowsum && gg.splitk >= kRsPartialMin && g.ws)
+  hipLaunchKernelGGL(pick_kernel<T>(g, tile, dma, vec), grid, dim3(tile.nwm * tile.nwn * 64), 0, s, gg, kchunk, evec, sk);
+  // the bias-gradient partials (after the slab, if any): only gemm_dma_kernel writes them; the register-staged
+  // kernels add the bias gradient atomically into rowsum and leave the workspace untouched
+  if (dma && g.rowsum && gg.splitk >= kRsPartialMin && g.ws)
     hipLaunchKernelGGL(rowsum_reduce_kernel, dim3(dfk_cdiv(g.M, 64)), dim3(1024), 0, s,
                        reinterpret_cast<const float*>(g.ws) + (g.atomic ? 0L : (long)gg.splitk * g.M * g.N), gg.splitk,
                        g.M, g.rowsum);
@@ -1199,16 +1129,15 @@ __device__ __forceinline__ i32x8 frag_mx(const uint8_t* img, int r0, int lane) {
   return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
 }
 
-template <int WT, int NWM, int NWN, int S, bool MXO>
+template <int WT, int NWM, int NWN, bool MXO>
 __global__ __launch_bounds__(NWM * NWN * 64) void gemm_mx_kernel(const dfk_gemm_args g, const dfk_mx_operand ma,
                                                                  const dfk_mx_operand mb, int evec) {
-  constexpr int NWV = NWM * NWN, BM = NWM * WT, BN = NWN * WT, MI = WT / 16, BK = 128;
+  constexpr int NWV = NWM * NWN, BM = NWM * WT, BN = NWN * WT, MI = WT / 16, BK = 128, S = kStages;
   constexpr int RW = (BM + BN) / NWV;                 // scale rows DMA'd per wave (one 4-B-per-lane instruction)
   static_assert(RW <= 64 && BM % RW == 0, "scale DMA split");
   constexpr int STAGE = (BM + BN) * BK + NWV * 256;   // operand images + per-wave 256-B scale slots (bytes)
   constexpr int ES = WT + 4;
   constexpr int SMEM = S * STAGE > NWV * WT * ES * 4 ? S * STAGE : NWV * WT * ES * 4;
-  constexpr int LPT = Dma8<BM, NWV>::NI + Dma8<BN, NWV>::NI + 1;   // DMA instructions per wave per k-tile
   __shared__ __attribute__((aligned(16))) float smem_f[SMEM / 4];   // the one LDS object (staging + epilogue)
   uint8_t* smem = reinterpret_cast<uint8_t*>(smem_f);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1257,11 +1186,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_mx_kernel(const dfk_gemm_
   for (int d = 0; d < S - 1; ++d)
     if (d < ntile) issue(d, smem + d * STAGE);
   for (int t = 0; t < ntile; ++t) {
-    if constexpr (S == 3) {
-      if (t + 1 < ntile) wait_vm<LPT>(); else wait_vm<0>();
-    } else {
-      wait_vm<0>();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1401,14 +1326,6 @@ __global__ __launch_bounds__(256) void mx_quant_t_kernel(const T* __restrict__ x
   }
 }
 
-// epilogue 16-B path legal for g (8-element groups of C / residual / aux / bias rows stay 16-B aligned)
-bool epi_vec(const dfk_gemm_args& g) {
-  return !g.c_f32 && aligned16(g.c) && g.ldc % 8 == 0 && g.cbs0 % 8 == 0 && g.cbs1 % 8 == 0 &&
-         (!g.bias || (aligned16(g.bias) && g.bias_bs1 % 8 == 0)) &&
-         (!g.residual || (aligned16(g.residual) && g.ldr % 8 == 0 && g.rbs0 % 8 == 0 && g.rbs1 % 8 == 0)) &&
-         (!g.aux || (aligned16(g.aux) && g.ldaux % 8 == 0));
-}
-
 }  // namespace
 
 // Arrival tickets of the in-launch split-K combine: one zeroed arena of counters per device, handed out in
@@ -1466,12 +1383,10 @@ bool dw_group_plan(const dfk_gemm_args& g, DwProblem& r, int& wt) {
   if (g.splitk < 1 || (g.atomic != 0) != (g.splitk > 1) || (!g.atomic && g.beta != 1.f)) return false;
   if (g.rowsum && g.splitk >= kRsPartialMin) return false;   // partials + rowsum_reduce_kernel: launched singly
   if (g.K >= 16384) return false;                            // dfk_wgrad_try's range
-  if (!dma_ok(g) || !view_vec(g.a, 8) || !view_vec(g.b, 8) || g.M % 8 || g.N % 8) return false;
+  if (!dma_vec(g)) return false;
   if (g.a.ld > 0x7fffffffL || g.b.ld > 0x7fffffffL || g.ldc > 0x7fffffffL) return false;
-  // (the tile-shape tuning knobs of launch() that can move a dW off the 4-wave tiles: such runs launch singly)
-  if (auto_splitk<bf16raw>(g) != 1 || getenv("DFK_GEMM_T256") || getenv("DFK_GEMM_T32X")) return false;
-  wt = pick_wt(g);
-  if ((wt != 32 && wt != 64) || dw_stages(wt) != 2) return false;
+  if (auto_splitk(g) != 1) return false;
+  wt = pick_tile(g).wt;   // k-major A: a 4-wave tile
   const long gx = dfk_cdiv(g.N, 2 * wt), gy = dfk_cdiv(g.M, 2 * wt);
   if (gy > 65535 || g.splitk > 65535 || gx * gy * g.splitk > (1L << 24)) return false;
   r.a = g.a.ptr;
@@ -1549,13 +1464,10 @@ extern "C" int dfk_gemm_dw_group(const dfk_gemm_args* problems, int32_t n, hipSt
 
 extern "C" int64_t dfk_gemm_workspace(const dfk_gemm_args* g) {
   if (!g) return -1;
-  const int autos = g->splitk > 1 && !g->atomic ? g->splitk
-                    : (g->dtype == DFK_BF16 ? auto_splitk<bf16raw>(*g) : auto_splitk<float>(*g));
+  const int autos = g->splitk > 1 && !g->atomic ? g->splitk : auto_splitk(*g);
   // per-split bias-gradient partials (gemm_dma_kernel RS, i.e. the LDS-DMA vector path only), after the split
   // slabs if there are any
-  const bool dmav = g->dtype == DFK_BF16 && dma_ok(*g) && view_vec(g->a, 8) && view_vec(g->b, 8) &&
-                    (g->a_kmajor ? g->M : g->K) % 8 == 0 && (g->b_kmajor ? g->N : g->K) % 8 == 0;
-  const int64_t rs = !dmav || !g->rowsum ? 0
+  const int64_t rs = !dma_vec(*g) || !g->rowsum ? 0
                      : (g->atomic && g->splitk >= kRsPartialMin ? (int64_t)g->splitk * g->M * 4
                                                                 : (autos >= kRsPartialMin ? (int64_t)autos * g->M * 4 : 0));
   if (autos <= 1) return rs;
@@ -1601,13 +1513,13 @@ extern "C" int dfk_gemm_mx(const dfk_gemm_args* gp, const dfk_mx_operand* a, con
   if (tiles128 < 1024) {   // 64 x 64 tiles for grids that 128 x 128 tiles cannot spread over the chip
     dim3 grid(dfk_cdiv(g.N, 64), dfk_cdiv(g.M, 64));
     if (grid.y > 65535) return DFK_EINVAL;
-    if (mxo) hipLaunchKernelGGL((gemm_mx_kernel<32, 2, 2, 2, true>), grid, dim3(256), 0, s, g, *a, *b, evec);
-    else hipLaunchKernelGGL((gemm_mx_kernel<32, 2, 2, 2, false>), grid, dim3(256), 0, s, g, *a, *b, evec);
+    if (mxo) hipLaunchKernelGGL((gemm_mx_kernel<32, 2, 2, true>), grid, dim3(256), 0, s, g, *a, *b, evec);
+    else hipLaunchKernelGGL((gemm_mx_kernel<32, 2, 2, false>), grid, dim3(256), 0, s, g, *a, *b, evec);
   } else {
     dim3 grid(dfk_cdiv(g.N, 128), dfk_cdiv(g.M, 128));
     if (grid.y > 65535) return DFK_EINVAL;
-    if (mxo) hipLaunchKernelGGL((gemm_mx_kernel<64, 2, 2, 2, true>), grid, dim3(256), 0, s, g, *a, *b, evec);
-    else hipLaunchKernelGGL((gemm_mx_kernel<64, 2, 2, 2, false>), grid, dim3(256), 0, s, g, *a, *b, evec);
+    if (mxo) hipLaunchKernelGGL((gemm_mx_kernel<64, 2, 2, true>), grid, dim3(256), 0, s, g, *a, *b, evec);
+    else hipLaunchKernelGGL((gemm_mx_kernel<64, 2, 2, false>), grid, dim3(256), 0, s, g, *a, *b, evec);
   }
   DFK_CHECK_LAUNCH();
   return 0;
