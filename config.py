@@ -77,6 +77,10 @@ def build_parser():
     parser.add_argument('--log_dir', type=str, default=None)
     # MI355X build
     parser.add_argument('--config', type=str, default='c2', choices=['c1', 'c2', 'c4', 'c5'])
+    parser.add_argument('--w2v_config', type=str, default=None, metavar='PATH',
+                        help='wav2vec2 config JSON of the waveform slot (default: the wav2vec2-base one in '
+                             'deepfake_amd/models/; deepfake_amd/models/w2v_large_config.json is the layer-norm / '
+                             'pre-norm wav2vec2-large-lv60 layout); w2v_layers of --config still sets the layer count')
     parser.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'fp32'])
     parser.add_argument('--graph', dest='graph', action='store_true', default=True)
     parser.add_argument('--no-graph', dest='graph', action='store_false')

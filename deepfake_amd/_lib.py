@@ -127,6 +127,13 @@ SIGNATURES = {
     "dfk_w2v_conv0_fwd_workspace": [_I64, _I64],
     "dfk_w2v_conv0_bwd": [_VP, _I64, _I64, _VP, _VP, _VP, _F, _VP, _VP, C.c_int, _VP, _I64, _VP, _VP, _VP, _VP],
     "dfk_w2v_conv0_bwd_workspace": [_I64, _I64],
+    "dfk_w2v_conv0_ln_fwd": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _F, _VP, _VP, C.c_int, _VP],
+    "dfk_w2v_conv0_ln_bwd": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, _VP, _I64, _VP, _VP, _VP, _VP,
+                             _VP],
+    "dfk_w2v_conv0_ln_bwd_workspace": [_I64, _I64],
+    "dfk_w2v_ln_gelu_fwd": [_VP, _I64, _I64, _VP, _VP, _F, _VP, _VP, C.c_int, _VP],
+    "dfk_w2v_ln_gelu_bwd": [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, C.c_int, _VP, _I64, _VP, _VP, _VP, _VP],
+    "dfk_w2v_ln_gelu_bwd_workspace": [_I64],
     "dfk_sgd_step_runs": [_VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _F, _F, _F, _F, _VP, _VP],
     "dfk_sgd_step": [_VP, _VP, _VP, _VP, _I64, _VP, _F, _F, _F, C.c_int, _VP, _F, _VP, _VP],
     "dfk_adamw_prelude": [_VP, _VP, _I32, _VP, _I32, C.c_double, C.c_double, _VP],
@@ -179,7 +186,18 @@ for _n in ("dfk_sgd_step", "dfk_sgd_step_runs", "dfk_adamw_step", "dfk_adamw_ste
     SIGNATURES[_n + "_clip"] = SIGNATURES[_n][:-1] + [_VP, SIGNATURES[_n][-1]]
 
 _lib = None
-RESTYPES = {"dfk_mel_workspace": _I64, "dfk_mel_resampled_workspace": _I64, "dfk_w2v_conv0_bwd_workspace": _I64, "dfk_w2v_conv0_fwd_workspace": _I64, "dfk_layernorm_bwd_workspace": _I64, "dfk_wattn_bwd_workspace": _I64, "dfk_wattn_table_workspace": _I64, "dfk_gemm_workspace": _I64}
+RESTYPES = {n: _I64 for n in (
+    "dfk_mel_workspace",
+    "dfk_mel_resampled_workspace",
+    "dfk_w2v_conv0_bwd_workspace",
+    "dfk_w2v_conv0_fwd_workspace",
+    "dfk_w2v_conv0_ln_bwd_workspace",
+    "dfk_w2v_ln_gelu_bwd_workspace",
+    "dfk_layernorm_bwd_workspace",
+    "dfk_wattn_bwd_workspace",
+    "dfk_wattn_table_workspace",
+    "dfk_gemm_workspace",
+)}
 
 
 def lib():

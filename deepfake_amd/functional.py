@@ -598,6 +598,83 @@ class ConvGeluFn(torch.autograd.Function):
         return dx, dw, None
 
 
+class W2VConv0LNFn(torch.autograd.Function):
+    """wav2vec2 layer-norm conv layer 0: Conv1d(1->512,k10,s5) (+ bias) + LayerNorm(512) per frame + GELU
+    (HF modeling_wav2vec2.py:275-299) -> channels-last [B, T0, 512].  bias may be None (conv_bias false)."""
+
+    @staticmethod
+    def forward(ctx, wave, weight, bias, gamma, beta, eps, dtype):
+        w = weight.detach().float().reshape(512, 10).contiguous()
+        f32 = lambda p: None if p is None else p.detach().float()   # noqa: E731
+        out, stats = K.w2v_conv0_ln_fwd(wave.float().contiguous(), w, f32(bias), f32(gamma), f32(beta), eps, dtype)
+        for i, p in enumerate((weight, bias, gamma, beta)):
+            if p is not None:
+                grad_use(ctx, 1 + i, p)
+        ctx.save_for_backward(wave, w, weight, bias, gamma, beta, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        wave, w, weight, bias, gamma, beta, stats = ctx.saved_tensors
+        f32 = lambda p: None if p is None else p.detach().float()   # noqa: E731
+        dw, dg, dbe = grad_sink(weight), grad_sink(gamma), grad_sink(beta)
+        db = grad_sink(bias) if bias is not None else None
+        K.w2v_conv0_ln_bwd(wave.float().contiguous(), w, f32(bias), f32(gamma), f32(beta), stats, dout.contiguous(),
+                           dw.view(512, 10), db, dg, dbe)
+        return (None, grad_done(weight, dw), grad_done(bias, db) if bias is not None else None, grad_done(gamma, dg),
+                grad_done(beta, dbe), None, None)
+
+
+class ConvLNGeluFn(torch.autograd.Function):
+    """Channels-last Conv1d(Cin->512, k, stride s) (+ bias) + LayerNorm(512) per frame + GELU (HF
+    modeling_wav2vec2.py:275-299, conv layers 1..6 of the layer-norm feature encoder): ConvGeluFn's implicit GEMM
+    with a bias epilogue and no activation, then the ln_gelu row kernel; the backward is ln_gelu_bwd followed by
+    ConvGeluFn's dW and per-tap dX GEMMs."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, stride, eps):
+        B, Tin, Cin = x.shape
+        Cout, _, k = weight.shape
+        Tout = (Tin - k) // stride + 1
+        dt = x.dtype
+        w2 = weight.detach().permute(0, 2, 1).reshape(Cout, k * Cin).to(dt).contiguous()
+        pre = torch.empty(B, Tout, Cout, device=x.device, dtype=dt)
+        K.gemm(x, Cin, False, w2, k * Cin, False, Tout, Cout, k * Cin, pre, Cout, dtype=K.L.dt(x),
+               bias=compute_weight(bias, dt), nz=(B, 1), a_bs=(Tin * Cin, 0), c_bs=(Tout * Cout, 0),
+               a_conv=(Cin, stride, 0, Tin))
+        y, stats = K.w2v_ln_gelu_fwd(pre, gamma.detach().float(), beta.detach().float(), eps)
+        for i, p in ((2, bias), (3, gamma), (4, beta)):
+            if p is not None:
+                grad_use(ctx, i, p)
+        ctx.save_for_backward(x, w2, pre, stats, bias, gamma, beta)
+        ctx.meta = (stride, k, Cin, Cout, Tin, Tout)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w2, pre, stats, bias, gamma, beta = ctx.saved_tensors
+        stride, k, Cin, Cout, Tin, Tout = ctx.meta
+        B = x.shape[0]
+        dt = K.L.dt(x)
+        dg, dbe = grad_sink(gamma), grad_sink(beta)
+        db = grad_sink(bias) if bias is not None else None
+        dpre = K.w2v_ln_gelu_bwd(dy.contiguous(), pre, gamma.detach().float(), beta.detach().float(), stats, dg, dbe, db)
+        dw2 = torch.zeros(Cout, k * Cin, device=x.device)
+        tiles = -(-Cout // 128) * -(-(k * Cin) // 128)
+        K.gemm(dpre, Cout, True, x, Cin, True, Cout, k * Cin, Tout, dw2, k * Cin, dtype=dt, c_f32=True, atomic=True,
+               splitk=max(1, min(K.splitk_for(tiles * B, Tout, 128), 16)), nz=(B, 1), a_bs=(Tout * Cout, 0),
+               b_bs=(Tin * Cin, 0), b_conv=(Cin, stride, 0, Tin))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.zeros(B, Tin, Cin, device=x.device, dtype=x.dtype)
+            for kk in range(k):  # col2im: tap kk of output t lands on input row stride*t + kk
+                K.gemm(dpre, Cout, False, w2[:, kk * Cin:], k * Cin, True, Tout, Cin, Cout, dx[:, kk:], stride * Cin,
+                       dtype=dt, beta=1.0, nz=(B, 1), a_bs=(Tout * Cout, 0), c_bs=(Tin * Cin, 0))
+        dw = dw2.view(Cout, k, Cin).permute(0, 2, 1)
+        return (dx, dw, grad_done(bias, db) if bias is not None else None, grad_done(gamma, dg), grad_done(beta, dbe),
+                None, None)
+
+
 def _posconv_gemm_fwd(x, w2, bias, groups, k):
     """y = x + gelu(conv(x) + b) as the implicit GEMM per (clip, group); returns (y, pre-activation)."""
     B, T, C = x.shape

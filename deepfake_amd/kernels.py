@@ -587,6 +587,53 @@ def w2v_conv0_bwd(wave, w, gamma, beta, eps, stats, dout, dw, dgamma, dbeta):
                                       L.ptr(dbeta), L.stream()), "w2v_conv0_bwd")
 
 
+def w2v_conv0_ln_fwd(wave, w, bias, gamma, beta, eps, dtype):
+    """Conv1d(1->512,k10,s5) (+ bias) + LayerNorm(512) + GELU -> ([B, T0, 512] dtype, row stats [B*T0, 2])."""
+    B, S = wave.shape
+    T0 = (S - 10) // 5 + 1
+    out = torch.empty(B, T0, 512, device=wave.device, dtype=dtype)
+    stats = torch.empty(B * T0, 2, device=wave.device, dtype=torch.float32)
+    L.check(L.lib().dfk_w2v_conv0_ln_fwd(L.ptr(wave), B, S, L.ptr(w), L.ptr(bias), L.ptr(gamma), L.ptr(beta),
+                                         float(eps), L.ptr(stats), L.ptr(out), L.dt(out), L.stream()),
+            "w2v_conv0_ln_fwd")
+    return out, stats
+
+
+def w2v_conv0_ln_bwd(wave, w, bias, gamma, beta, stats, dout, dw, dbias, dgamma, dbeta):
+    """dw, dbias (None without a bias), dgamma, dbeta += (fixed-order sums: bitwise repeatable)."""
+    B, S = wave.shape
+    scratch = torch.empty(max(L.lib().dfk_w2v_conv0_ln_bwd_workspace(B, S) // 4, 4), device=wave.device,
+                          dtype=torch.float32)
+    L.check(L.lib().dfk_w2v_conv0_ln_bwd(L.ptr(wave), B, S, L.ptr(w), L.ptr(bias), L.ptr(gamma), L.ptr(beta),
+                                         L.ptr(stats), L.ptr(dout), L.dt(dout), L.ptr(scratch), scratch.numel() * 4,
+                                         L.ptr(dw), L.ptr(dbias), L.ptr(dgamma), L.ptr(dbeta), L.stream()),
+            "w2v_conv0_ln_bwd")
+
+
+def w2v_ln_gelu_fwd(x, gamma, beta, eps):
+    """gelu(LayerNorm(x)) over the last dim (512) of a contiguous x -> (out like x, row stats [rows, 2])."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    out = torch.empty_like(x)
+    stats = torch.empty(rows, 2, device=x.device, dtype=torch.float32)
+    L.check(L.lib().dfk_w2v_ln_gelu_fwd(L.ptr(x), rows, C, L.ptr(gamma), L.ptr(beta), float(eps), L.ptr(stats),
+                                        L.ptr(out), L.dt(x), L.stream()), "w2v_ln_gelu_fwd")
+    return out, stats
+
+
+def w2v_ln_gelu_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, dbias):
+    """-> dx (like x); dgamma, dbeta, dbias (= colsum(dx)) += where given."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    dx = torch.empty_like(x)
+    scratch = torch.empty(max(L.lib().dfk_w2v_ln_gelu_bwd_workspace(rows) // 4, 4), device=x.device,
+                          dtype=torch.float32)
+    L.check(L.lib().dfk_w2v_ln_gelu_bwd(L.ptr(dy), L.ptr(x), rows, C, L.ptr(gamma), L.ptr(beta), L.ptr(stats),
+                                        L.ptr(dx), L.dt(x), L.ptr(scratch), scratch.numel() * 4, L.ptr(dgamma),
+                                        L.ptr(dbeta), L.ptr(dbias), L.stream()), "w2v_ln_gelu_bwd")
+    return dx
+
+
 def gelu_bwd(dy, pre, out=None):
     if out is None:
         out = torch.empty_like(dy)

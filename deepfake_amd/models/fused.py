@@ -45,8 +45,14 @@ CONFIGS = {
 }
 
 
-def build_fused(cfg, args=None, w2v_config=W2V_CONFIG, compute_dtype=torch.float32, regularize=False, fp8=False):
-    """The north-star fused model.  regularize=False (parity / default): every dropout, DropPath,
+def _w2v_config_path(args, default=W2V_CONFIG):
+    """--w2v_config PATH (config.py) when given, else the committed wav2vec2-base JSON."""
+    return getattr(args, "w2v_config", None) or default
+
+
+def build_fused(cfg, args=None, w2v_config=None, compute_dtype=torch.float32, regularize=False, fp8=False):
+    """The north-star fused model.  The waveform slot's checkpoint family comes from w2v_config, else from
+    args.w2v_config (--w2v_config), else the wav2vec2-base JSON.  regularize=False (parity / default): every dropout, DropPath,
     SpecAugment and LayerDrop off (Q12).  regularize=True: the reference's training regularisers — VST
     drop_path_rate 0.2 (SwinTransformer3D default, video_swin_transformer.py:500), SwinV2 0.1
     (swin_transformer2d.py:506), the wav2vec2-base checkpoint config's dropouts / LayerDrop /
@@ -60,12 +66,12 @@ def build_fused(cfg, args=None, w2v_config=W2V_CONFIG, compute_dtype=torch.float
         vkw["drop_path_rate"], mkw["drop_path_rate"] = 0.2, 0.1
     vst = SwinTransformer3D(**vkw)
     mel = SwinTransformerV2(**mkw)
-    wcfg = Wav2Vec2Config.from_json_file(w2v_config, num_hidden_layers=cfg["w2v_layers"])
+    wcfg = Wav2Vec2Config.from_json_file(w2v_config or _w2v_config_path(args), num_hidden_layers=cfg["w2v_layers"])
     if not regularize:
         wcfg = wcfg.deterministic()
-    pa = Audio2D(args, Wav2Vec2Model(wcfg), num_classes=1, use_feat=True)
+    pa = Audio2D(args, Wav2Vec2Model(wcfg), in_feat=wcfg.hidden_size, num_classes=1, use_feat=True)
     m = FusionModel(args, VSTFeat(vst), mel, pa, out_dim=1, video_dim=cfg["video_dim"], audio_dim=cfg["audio_dim"],
-                    paudio_dim=768)
+                    paudio_dim=wcfg.hidden_size)
     if fp8:   # C4: MX-fp8 video-trunk GEMMs (bf16 compute everywhere else)
         st = os.environ.get("DFK_FP8_STAGES")   # A/B knob: 0-based stages on MX-fp8, e.g. "2,3" (default) or "0,1,2,3"
         set_fp8(m, tuple(int(v) for v in st.split(",") if v.strip()) if st is not None else cfg.get("fp8_stages", (2, 3)))
@@ -77,8 +83,9 @@ def build_model(args, compute_dtype=torch.float32):
       fused  -> FusionModel(VSTFeat(SwinTransformer3D), SwinTransformerV2(use_feat), Audio2D(wav2vec2))
       video  -> VideoClassifier (SwinTransformer3D + mean-pool Mlp head, video_swin_transformer.py:688-793)
       audio  -> SwinTransformerV2(num_classes=1, 128; 2,2,18,2) (train.py:35)
-      paudio -> Audio2D(wav2vec2-base) (train.py:39-41)
-    Shapes come from --config; regularisers follow --deterministic."""
+      paudio -> Audio2D(wav2vec2) (train.py:39-41)
+    Shapes come from --config, the wav2vec2 family from --w2v_config (default: wav2vec2-base); regularisers follow
+    --deterministic."""
     from .video_swin_transformer import VideoClassifier
     cfg = CONFIGS[getattr(args, "config", "c2")]
     reg = not getattr(args, "deterministic", False)
@@ -102,8 +109,9 @@ def build_model(args, compute_dtype=torch.float32):
         mkw = dict(cfg["mel"], use_feat=False, drop_path_rate=0.1 if reg else 0.0)
         return set_compute_dtype(SwinTransformerV2(**mkw), compute_dtype)
     if args.modality == "paudio":
-        wcfg = Wav2Vec2Config.from_json_file(W2V_CONFIG, num_hidden_layers=cfg["w2v_layers"])
+        wcfg = Wav2Vec2Config.from_json_file(_w2v_config_path(args), num_hidden_layers=cfg["w2v_layers"])
         if not reg:
             wcfg = wcfg.deterministic()
-        return set_compute_dtype(Audio2D(args, Wav2Vec2Model(wcfg), num_classes=1), compute_dtype)
+        return set_compute_dtype(Audio2D(args, Wav2Vec2Model(wcfg), in_feat=wcfg.hidden_size, num_classes=1),
+                                 compute_dtype)
     raise ValueError(f"unknown modality {args.modality!r}")

@@ -1,6 +1,6 @@
-"""wav2vec2-base on MI355X with HF-compatible state_dict keys (drop-in for the
-``transformers.Wav2Vec2Model`` the reference builds at train.py:46 and wraps in
-Audio2D, audioTransformer.py:5-30).  Restates transformers 5.15.0
+"""wav2vec2 (base, and the layer-norm / pre-norm large family) on MI355X with
+HF-compatible state_dict keys (drop-in for the ``transformers.Wav2Vec2Model``
+the reference builds at train.py:46 and wraps in Audio2D, audioTransformer.py:5-30).  Restates transformers 5.15.0
 models/wav2vec2/modeling_wav2vec2.py (HF/ below) on HIP kernels:
 
   conv0 + GroupNorm + GELU        dfk_w2v_conv0_*   (HF/:302-323)
@@ -9,6 +9,12 @@ models/wav2vec2/modeling_wav2vec2.py (HF/ below) on HIP kernels:
   weight-normed grouped pos-conv  implicit GEMM per (clip, group), + residual (HF/:326-380,689)
   12 post-LN encoder layers       fused qkv GEMM, whole-sequence attention kernel,
                                   out_proj+residual, LN, FFN(+residual), LN (HF/:575-608)
+
+With feat_extract_norm == "layer" and do_stable_layer_norm (wav2vec2-large-lv60, XLS-R, HuBERT-large configs):
+
+  conv0 (+bias) + LayerNorm + GELU    dfk_w2v_conv0_ln_*  (HF/:275-299), one launch each way
+  conv1..6 (+bias) + LayerNorm + GELU implicit-GEMM conv with a bias epilogue, then dfk_w2v_ln_gelu_*
+  pre-LN encoder layers + final LN    the same ops in the other order (HF/:611-654, :729-802)
 
 Training-mode regularisers of the checkpoint config (HF/ sites, all drawn on the
 device, deepfake_amd.rng): feat_proj_dropout after the projection GEMM (:433),
@@ -77,31 +83,58 @@ class Wav2Vec2Config:
 
 
 class _ConvLayer(nn.Module):
-    def __init__(self, cin, cout, k, s, group_norm):
+    """One feature-encoder layer's parameters under HF's names: ``norm`` is None (HF/:253-272), "group"
+    (GroupNorm, HF/:302-323) or "layer" (LayerNorm over the channels of each frame, HF/:275-299; built without
+    an eps argument there, so nn.LayerNorm's default 1e-5 and not config.layer_norm_eps)."""
+
+    def __init__(self, cin, cout, k, s, norm, bias=False):
         super().__init__()
-        self.conv = nn.Conv1d(cin, cout, kernel_size=k, stride=s, bias=False)
-        if group_norm:
+        self.conv = nn.Conv1d(cin, cout, kernel_size=k, stride=s, bias=bias)
+        if norm == "group":
             self.layer_norm = nn.GroupNorm(num_groups=cout, num_channels=cout, affine=True)
+        elif norm == "layer":
+            self.layer_norm = nn.LayerNorm(cout, elementwise_affine=True)
         self.stride = s
 
 
 class Wav2Vec2FeatureEncoder(nn.Module):
-    """HF/:382-419 (feat_extract_norm == "group")."""
+    """HF/:382-419: feat_extract_norm == "group" (wav2vec2-base: GroupNorm on layer 0 only, no conv bias) or
+    "layer" (wav2vec2-large-lv60 / XLS-R / HuBERT-large: LayerNorm on all seven layers, conv_bias either way)."""
 
     def __init__(self, config):
         super().__init__()
-        if config.feat_extract_norm != "group" or config.conv_bias or config.conv_dim[0] != 512 \
-                or config.conv_kernel[0] != 10 or config.conv_stride[0] != 5:
-            raise NotImplementedError("only the wav2vec2-base feature encoder (group norm, 512x10/5 conv0)")
+        if config.feat_extract_norm not in ("group", "layer"):
+            raise NotImplementedError(f"feat_extract_norm {config.feat_extract_norm!r}")
+        if config.feat_extract_norm == "group" and config.conv_bias:
+            raise NotImplementedError("group-norm feature encoder with conv_bias")
+        if config.conv_dim[0] != 512 or config.conv_kernel[0] != 10 or config.conv_stride[0] != 5:
+            raise NotImplementedError("only a 512x10/5 conv0")
+        self.layer_norm_path = config.feat_extract_norm == "layer"
+        if self.layer_norm_path and any(d != 512 for d in config.conv_dim):
+            raise NotImplementedError("layer-norm feature encoder with a conv_dim other than 512")
         dims = [1] + list(config.conv_dim)
-        self.conv_layers = nn.ModuleList([
-            _ConvLayer(dims[i], dims[i + 1], config.conv_kernel[i], config.conv_stride[i], i == 0)
-            for i in range(len(config.conv_dim))])
+        if self.layer_norm_path:
+            self.conv_layers = nn.ModuleList([
+                _ConvLayer(dims[i], dims[i + 1], config.conv_kernel[i], config.conv_stride[i], "layer",
+                           bool(config.conv_bias))
+                for i in range(len(config.conv_dim))])
+        else:
+            self.conv_layers = nn.ModuleList([
+                _ConvLayer(dims[i], dims[i + 1], config.conv_kernel[i], config.conv_stride[i],
+                           "group" if i == 0 else None)
+                for i in range(len(config.conv_dim))])
         self.compute_dtype = torch.float32
 
     def forward(self, input_values):
         """[B, S] fp32 -> channels-last [B, T, 512] (compute dtype)."""
         l0 = self.conv_layers[0]
+        if self.layer_norm_path:
+            x = Fn.W2VConv0LNFn.apply(input_values, l0.conv.weight, l0.conv.bias, l0.layer_norm.weight,
+                                      l0.layer_norm.bias, l0.layer_norm.eps, self.compute_dtype)
+            for layer in self.conv_layers[1:]:
+                x = Fn.ConvLNGeluFn.apply(x, layer.conv.weight, layer.conv.bias, layer.layer_norm.weight,
+                                          layer.layer_norm.bias, layer.stride, layer.layer_norm.eps)
+            return x
         x = Fn.W2VConv0Fn.apply(input_values, l0.conv.weight, l0.layer_norm.weight, l0.layer_norm.bias,
                                 l0.layer_norm.eps, self.compute_dtype)
         for layer in self.conv_layers[1:]:
@@ -221,14 +254,19 @@ class Wav2Vec2EncoderLayer(nn.Module):
 class Wav2Vec2Encoder(nn.Module):
     """HF/:657-727 (no attention mask: equal-length clips, Q13)."""
 
+    layer_class = Wav2Vec2EncoderLayer
+
+    stable_layer_norm = False   # the config's do_stable_layer_norm this class implements
+
     def __init__(self, config):
         super().__init__()
-        if config.do_stable_layer_norm:
-            raise NotImplementedError("stable-layer-norm encoder")
+        if bool(config.do_stable_layer_norm) != self.stable_layer_norm:
+            raise NotImplementedError(f"{type(self).__name__} with do_stable_layer_norm={config.do_stable_layer_norm}"
+                                      " (Wav2Vec2Model picks the encoder class by it)")
         self.pos_conv_embed = Wav2Vec2PositionalConvEmbedding(config)
         self.layer_norm = nn.LayerNorm(config.hidden_size, eps=config.layer_norm_eps)
         self.dropout = rng.Drop(config.hidden_dropout)
-        self.layers = nn.ModuleList([Wav2Vec2EncoderLayer(config) for _ in range(config.num_hidden_layers)])
+        self.layers = nn.ModuleList([self.layer_class(config) for _ in range(config.num_hidden_layers)])
         # LayerDrop coins: rank-independent draws (every replica drops the same layers, so the SGD skip of a
         # dropped layer's parameters stays identical across data-parallel ranks); 1 = run, 0 = skip
         self.layerdrop = rng.Drop(config.layerdrop, shared=True)
@@ -252,6 +290,10 @@ class Wav2Vec2Encoder(nn.Module):
         B, T, C = h.shape
         d = self.dropout.spec() if self.dropout.active(self.training) else None
         x = Fn.layer_norm(self.pos_conv_embed.add_to(h.contiguous()), self.layer_norm, drop=d).reshape(B * T, C)
+        return self._run_layers(x, B, T).view(B, T, C)
+
+    def _run_layers(self, x, B, T):
+        """The layers on x [B*T, C] under LayerDrop (HF/:700-706)."""
         lds = self.layerdrop.active(self.training)
         if lds:
             K.layerdrop_flags(self.layerdrop.spec(), self.layer_keep, self.layer_used)
@@ -263,11 +305,46 @@ class Wav2Vec2Encoder(nn.Module):
                 x = Fn.LayerSelectFn.apply(y, x, self.layer_keep[i:i + 1])
             else:
                 x = torch.where(self.layer_keep[i] > 0, y, x)
-        return x.view(B, T, C)
+        return x
+
+
+class Wav2Vec2EncoderLayerStableLayerNorm(Wav2Vec2EncoderLayer):
+    """HF/:611-654 (pre-LN; do_stable_layer_norm): the modules and parameter names of the post-LN layer in another
+    order, h = h + dropout(out_proj(attn(layer_norm(h)))); h = h + FF(final_layer_norm(h)).  Each residual reads
+    its LayerNorm's skip alias, so h's two gradients meet inside the LN backward (as the Swin pre-norm blocks)."""
+
+    def forward(self, x, B, T):
+        tr = self.training
+        ff = self.feed_forward
+        spec = lambda d: d.spec() if d.active(tr) else None   # noqa: E731
+        xn, xs = Fn.layer_norm(x, self.layer_norm, skip=True)
+        a = self.attention.core(xn, B, T)
+        x = Fn.linear(a, self.attention.out_proj.weight, self.attention.out_proj.bias, residual=xs,
+                      drop=spec(self.dropout))
+        xn, xs = Fn.layer_norm(x, self.final_layer_norm, skip=True)
+        return Fn.mlp(xn, ff.intermediate_dense, ff.output_dense, residual=xs, drop_act=spec(ff.intermediate_dropout),
+                      drop_out=spec(ff.output_dropout))
+
+
+class Wav2Vec2EncoderStableLayerNorm(Wav2Vec2Encoder):
+    """HF/:729-802 (no attention mask: equal-length clips): h + pos_conv(h) -> dropout -> pre-LN layers under
+    LayerDrop -> encoder.layer_norm.  Parameter names, LayerDrop coins and SGD gates as the post-LN encoder."""
+
+    layer_class = Wav2Vec2EncoderLayerStableLayerNorm
+    stable_layer_norm = True
+
+    def forward(self, h):
+        B, T, C = h.shape
+        x = self.pos_conv_embed.add_to(h.contiguous()).reshape(B * T, C)
+        if self.dropout.active(self.training):
+            x = Fn.DropoutFn.apply(x, self.dropout.spec())
+        return Fn.layer_norm(self._run_layers(x, B, T), self.layer_norm).view(B, T, C)
 
 
 class Wav2Vec2Model(nn.Module):
-    """HF/:1244-1380 forward (SpecAugment / LayerDrop / dropouts must be off)."""
+    """HF/:1244-1380 forward.  config.do_stable_layer_norm picks the encoder (HF/:1255) and
+    config.feat_extract_norm the feature encoder.  Equal-length clips are the supported input: an attention_mask
+    (padded batches, and with it the per-clip normalisation the layer-norm checkpoints expect) raises."""
 
     def __init__(self, config):
         super().__init__()
@@ -276,7 +353,7 @@ class Wav2Vec2Model(nn.Module):
         self.feature_projection = Wav2Vec2FeatureProjection(config)
         if config.mask_time_prob > 0.0 or config.mask_feature_prob > 0.0:
             self.masked_spec_embed = nn.Parameter(torch.empty(config.hidden_size).uniform_())
-        self.encoder = Wav2Vec2Encoder(config)
+        self.encoder = (Wav2Vec2EncoderStableLayerNorm if config.do_stable_layer_norm else Wav2Vec2Encoder)(config)
 
         self.spec_site = rng.Drop(0.0)   # SpecAugment draws (site only)
         if config.mask_feature_prob > 0.0:

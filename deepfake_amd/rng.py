@@ -18,6 +18,7 @@ element masks of different clip shards are independent.
 Sites: every dropout site gets a distinct id at module construction
 (``new_site``), in construction order, so identically built replicas agree.
 """
+import contextlib
 import itertools
 
 import torch
@@ -38,6 +39,24 @@ def manual_seed(seed, rank=0):
     for st in _states.values():
         st[0], st[2] = _seed[0], _seed[1]
         st[1] = 0
+
+
+@contextlib.contextmanager
+def pinned(seed, first_site=1, rank=0):
+    """Draws that do not depend on what ran before in the process (tests of the regularisers): inside, the streams
+    are seeded with `seed` and the modules constructed get site ids from `first_site` on; on exit the seeds and
+    the site counter are what they were (the step counters stay where the run left them)."""
+    global _sites
+    old_seed, old_sites = list(_seed), _sites
+    _sites = itertools.count(int(first_site))
+    manual_seed(seed, rank)
+    try:
+        yield
+    finally:
+        _sites = old_sites
+        _seed[:] = old_seed
+        for st in _states.values():
+            st[0], st[2] = _seed[0], _seed[1]
 
 
 def state(device):

@@ -326,6 +326,43 @@ int dfk_w2v_conv0_bwd(const float* wave, int64_t B, int64_t S, const float* w, c
                       float* scratch, int64_t scratch_bytes, float* dw, float* dgamma, float* dbeta,
                       hipStream_t stream);
 
+/* wav2vec2 layer-norm feature encoder (HF modeling_wav2vec2.py:275-299, Wav2Vec2LayerNormConvLayer, all seven
+ * conv layers when feat_extract_norm == "layer"): conv (+ bias) -> LayerNorm over the 512 channels of each frame
+ * (eps as given; nn.LayerNorm's default 1e-5 at the HF site) -> GELU, channels-last.
+ *
+ * Layer 0, replacing conv + transpose + LayerNorm + transpose + GELU of HF :292-298 for Conv1d(1->512,k10,s5):
+ * wave [B,S] fp32, w [512,10], bias [512] or NULL (conv_bias false), gamma/beta [512] fp32; out [B,T0,512]
+ * (dtype), T0=(S-10)/5+1; stats [B*T0,2] fp32 (mean, rstd of every frame row) saved for the backward.  One
+ * launch; the conv output is never stored.  No sample at or past S and no frame past T0 is read.
+ * DFK_EINVAL before any launch for: a NULL operand, B <= 0 or > 65535, S < 10 or > 2^31, a dtype other than
+ * DFK_F32 / DFK_BF16, w/bias/gamma/beta/out not 16-B aligned, stats not 8-B aligned. */
+int dfk_w2v_conv0_ln_fwd(const float* wave, int64_t B, int64_t S, const float* w, const float* bias,
+                         const float* gamma, const float* beta, float eps, float* stats, void* out, int dtype,
+                         hipStream_t stream);
+/* backward of the above: recomputes the conv and xhat from stats; dw [512,10], dbias (NULL exactly when bias is),
+ * dgamma, dbeta (either may be NULL) fp32, all += (the contract of dfk_w2v_conv0_bwd: gradient accumulation adds
+ * into the same sinks).  The waveform gets no gradient.  scratch: 16-B aligned fp32 buffer of scratch_bytes >=
+ * dfk_w2v_conv0_ln_bwd_workspace(B, S) bytes: one row of partials per workgroup, summed into the sinks in a fixed
+ * order (no float atomics: bitwise repeatable).  The forward's argument rules hold; a smaller scratch returns
+ * DFK_EINVAL. */
+int64_t dfk_w2v_conv0_ln_bwd_workspace(int64_t B, int64_t S);
+int dfk_w2v_conv0_ln_bwd(const float* wave, int64_t B, int64_t S, const float* w, const float* bias,
+                         const float* gamma, const float* beta, const float* stats, const void* dout, int dtype,
+                         float* scratch, int64_t scratch_bytes, float* dw, float* dbias, float* dgamma, float* dbeta,
+                         hipStream_t stream);
+/* Layers 1..6, replacing transpose + LayerNorm + transpose + GELU of HF :294-298 on the conv GEMM's output with
+ * bias: x, out [rows, C] (dtype), C must be 512; stats [rows,2] fp32 (mean, rstd).  DFK_EINVAL for a NULL
+ * operand, rows <= 0, C != 512, a bad dtype, x/out/gamma/beta not 16-B aligned, stats not 8-B aligned. */
+int dfk_w2v_ln_gelu_fwd(const void* x, int64_t rows, int64_t C, const float* gamma, const float* beta, float eps,
+                        float* stats, void* out, int dtype, hipStream_t stream);
+/* backward: dx [rows, C] (dtype) = gradient of x; dgamma, dbeta, dbias = colsum(dx) fp32 (+=, any may be NULL)
+ * through per-workgroup partials in scratch (>= dfk_w2v_ln_gelu_bwd_workspace(rows) bytes, 16-B aligned) summed
+ * in a fixed order. */
+int64_t dfk_w2v_ln_gelu_bwd_workspace(int64_t rows);
+int dfk_w2v_ln_gelu_bwd(const void* dy, const void* x, int64_t rows, int64_t C, const float* gamma,
+                        const float* beta, const float* stats, void* dx, int dtype, float* scratch,
+                        int64_t scratch_bytes, float* dgamma, float* dbeta, float* dbias, hipStream_t stream);
+
 /* SwinV2 cosine-attention prologue (swin_transformer2d.py:154-157) on a [rows, 3C]
  * qkv buffer: q' = normalize(q)*scale[h], k' = normalize(k), v' = v, so the window
  * attention kernel then runs with scale 1; scale[h] = exp(min(logit_scale[h], max_log))

@@ -1,6 +1,6 @@
 // Host-side checks of libdfk under AddressSanitizer (CPU only; no kernel is launched).  Exercises the C ABI's
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
-// conv0, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
+// conv0 on both the group-norm and the layer-norm path, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
 // dims, the SGD and AdamW entry points' buffers / run table / hyper-parameters, the gradient-clipping entry points' slab /
 // coefficient / max_norm / run table, the parameter-group entry points' map / pairs / group count, the weight-EMA entry points' buffers / decay), which must return DFK_EINVAL before touching
 // the device.  Built and run by tools/asan/run.sh.
@@ -424,6 +424,95 @@ int main() {
     EXPECT(dfk_ema_swap(fx, fy, odd, 16, nullptr) == DFK_EINVAL);                         // shadow not 8-B aligned
     EXPECT(dfk_ema_swap(fx, fy, nullptr, (int64_t)1 << 43, nullptr) == DFK_EINVAL);
     EXPECT(dfk_ema_swap(fx, fy, nullptr, 0, nullptr) == 0);
+  }
+  {
+    // wav2vec2 layer-norm feature encoder: planners, then null operands, B <= 0, S < 10, rows <= 0, a channel
+    // count other than 512, misaligned pointers, a bad dtype, a short scratch: all before any launch
+    float* fx = reinterpret_cast<float*>(0x10000);
+    float* odd = reinterpret_cast<float*>(0x10004);
+    void* vx = reinterpret_cast<void*>(0x20000);
+    void* vodd = reinterpret_cast<void*>(0x20008);
+    const int64_t ws0 = dfk_w2v_conv0_ln_bwd_workspace(8, 64000);
+    EXPECT(ws0 > 0 && ws0 % 16 == 0);
+    EXPECT(dfk_w2v_conv0_ln_bwd_workspace(8, 9) == 0);
+    EXPECT(dfk_w2v_conv0_ln_bwd_workspace(0, 64000) == 0);
+    EXPECT(dfk_w2v_conv0_ln_bwd_workspace(2, 14) == (int64_t)4 * 2 * (512 * 10 + 3 * 512));   // T0 = 1: one workgroup per clip
+    const int64_t ws1 = dfk_w2v_ln_gelu_bwd_workspace(51192);
+    EXPECT(ws1 > 0 && ws1 % 16 == 0);
+    EXPECT(dfk_w2v_ln_gelu_bwd_workspace(0) == 0);
+    EXPECT(dfk_w2v_ln_gelu_bwd_workspace(-3) == 0);
+    EXPECT(dfk_w2v_ln_gelu_bwd_workspace(1) == (int64_t)4 * 3 * 512);
+    // conv0 forward
+    EXPECT(dfk_w2v_conv0_ln_fwd(nullptr, 8, 64000, fx, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, nullptr, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, nullptr, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, fx, nullptr, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, fx, fx, 1e-5f, nullptr, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, fx, fx, 1e-5f, fx, nullptr, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 0, 64000, fx, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, -1, 64000, fx, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 65536, 64000, fx, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 9, fx, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, fx, fx, 1e-5f, fx, vx, 7, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, odd, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, odd, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, odd, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, fx, odd, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, fx, fx, 1e-5f, odd, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_fwd(fx, 8, 64000, fx, fx, fx, fx, 1e-5f, fx, vodd, DFK_BF16, nullptr) == DFK_EINVAL);
+    // conv0 backward
+    EXPECT(dfk_w2v_conv0_ln_bwd(nullptr, 8, 64000, fx, fx, fx, fx, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, nullptr, vx, DFK_BF16, fx, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, nullptr, DFK_BF16, fx, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, vx, DFK_BF16, nullptr, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, vx, DFK_BF16, fx, ws0, nullptr, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);                                                    // no dw sink
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, vx, DFK_BF16, fx, ws0, fx, nullptr, fx, fx, nullptr) ==
+           DFK_EINVAL);                                                    // a bias without its sink
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, nullptr, fx, fx, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);                                                    // a bias sink without the bias
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, vx, DFK_BF16, fx, ws0 - 1, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);                                                    // short scratch
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, vx, DFK_BF16, odd, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);                                                    // scratch not 16-B aligned
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, vodd, DFK_BF16, fx, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 0, 64000, fx, fx, fx, fx, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 5, fx, fx, fx, fx, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, fx, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ln_bwd(fx, 8, 64000, fx, fx, fx, fx, fx, vx, -1, fx, ws0, fx, fx, fx, fx, nullptr) == DFK_EINVAL);
+    // row kernels
+    EXPECT(dfk_w2v_ln_gelu_fwd(nullptr, 100, 512, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, nullptr, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, fx, nullptr, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, fx, fx, 1e-5f, nullptr, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, fx, fx, 1e-5f, fx, nullptr, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 0, 512, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, -5, 512, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    for (int64_t badc : {(int64_t)0, (int64_t)256, (int64_t)768, (int64_t)1024})
+      EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, badc, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, fx, fx, 1e-5f, fx, vx, 2, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vodd, 100, 512, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, odd, fx, 1e-5f, fx, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, fx, fx, 1e-5f, odd, vx, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_fwd(vx, 100, 512, fx, fx, 1e-5f, fx, vodd, DFK_BF16, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(nullptr, vx, 100, 512, fx, fx, fx, vx, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, nullptr, 100, 512, fx, fx, fx, vx, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, nullptr, vx, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, nullptr, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vx, DFK_BF16, nullptr, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 0, 512, fx, fx, fx, vx, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 511, fx, fx, fx, vx, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vx, DFK_BF16, fx, 100, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vodd, vx, 100, 512, fx, fx, fx, vx, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vodd, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vx, DFK_BF16, odd, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vx, 9, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
   }
   EXPECT(dfk_cpb_bias_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 169, 512, 64, nullptr) != 0);
   std::printf("host_check: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);
