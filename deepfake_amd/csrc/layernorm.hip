@@ -367,14 +367,12 @@ long bwd_blocks(long rows, int C) {
   // at most 2048 workgroups, 512 from C = 512 up: their [blocks][2C] partial slab, summed by slab_colsum, grows
   // with C (tools/ln_bench.py, profiles/r4/r4s_ln_bwd_block_cap.txt: [6272, 768] 46 -> 25 us at 512, while the
   // narrow stage-1/2 rows need the 2048 workgroups: [401408, 96] 65 -> 84 us at 512)
-  static const long env = getenv("DFK_LN_BWD_BLOCKS") ? atol(getenv("DFK_LN_BWD_BLOCKS")) : 0;   // tuning runs
-  const long cap = env > 0 ? env : (C >= 512 ? 512 : 2048);
+  const long cap = C >= 512 ? 512 : 2048;
   // small LayerNorms (rows <= kLnSmallRows: the SwinV2 stage-3/4 and wav2vec2 ones): at most 128 workgroups adding
   // their dw/db partials atomically, no slab pass (r6b: 1568 x 512 14.1 -> 11.5 us, 1592 x 768 17.8 -> 15.9,
-  // 392 x 1024 16.5 -> 12.5; from 6k rows the slab + column pass stays faster).  DFK_LN_SMALL=n: n workgroups (A/B)
-  static const long small = getenv("DFK_LN_SMALL") ? atol(getenv("DFK_LN_SMALL")) : 128;
-  if (small > 0 && rows <= kLnSmallRows) return std::min<long>(small, dfk_cdiv(rows, 4L * (64 / L)));
-  return std::min<long>(cap, dfk_cdiv(rows, 4L * (64 / L)));
+  // 392 x 1024 16.5 -> 12.5; from 6k rows the slab + column pass stays faster)
+  constexpr long kLnSmallBlocks = 128;
+  return std::min<long>(rows <= kLnSmallRows ? kLnSmallBlocks : cap, dfk_cdiv(rows, 4L * (64 / L)));
 }
 
 template <typename T, int L, int V>

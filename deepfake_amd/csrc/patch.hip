@@ -441,23 +441,17 @@ extern "C" int dfk_patch_embed_fwd(const dfk_patch_embed_args* ap, hipStream_t s
   if (lds > 80 * 1024) return DFK_EINVAL;   // two workgroups per CU
   static bool attr_set = false;   // C = 128 (Swin-B) needs a little over 64 KB; once per process, never in a capture
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)pe_fwd_kernel<6, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     (void)hipFuncSetAttribute((const void*)pe_fwd_kernel<6, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)pe_fwd_kernel<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     (void)hipFuncSetAttribute((const void*)pe_fwd_kernel<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     attr_set = true;
   }
-  // persistent: two workgroups per CU (tuning knobs DFK_PE_PERCU / DFK_PE_DEPTH for tools/pe_bench.py)
-  static const int env_cu = getenv("DFK_PE_PERCU") ? atoi(getenv("DFK_PE_PERCU")) : 2;
-  static const int depth = getenv("DFK_PE_DEPTH") ? atoi(getenv("DFK_PE_DEPTH")) : 2;
-  const unsigned grid = (unsigned)std::min<long>(rows, 256L * std::max(1, env_cu));
-  if (a.C == 96) {
-    if (depth == 1) hipLaunchKernelGGL((pe_fwd_kernel<6, 1>), dim3(grid), dim3(NT), lds, s, a, g, rows);
-    else hipLaunchKernelGGL((pe_fwd_kernel<6, 2>), dim3(grid), dim3(NT), lds, s, a, g, rows);
-  } else {
-    if (depth == 1) hipLaunchKernelGGL((pe_fwd_kernel<8, 1>), dim3(grid), dim3(NT), lds, s, a, g, rows);
-    else hipLaunchKernelGGL((pe_fwd_kernel<8, 2>), dim3(grid), dim3(NT), lds, s, a, g, rows);
-  }
+  // persistent: two workgroups per CU, the clip rows of two token rows in flight (DEPTH 2)
+  constexpr long kPePerCu = 2;
+  const unsigned grid = (unsigned)std::min<long>(rows, 256L * kPePerCu);
+  if (a.C == 96)
+    hipLaunchKernelGGL((pe_fwd_kernel<6, 2>), dim3(grid), dim3(NT), lds, s, a, g, rows);
+  else
+    hipLaunchKernelGGL((pe_fwd_kernel<8, 2>), dim3(grid), dim3(NT), lds, s, a, g, rows);
   DFK_CHECK_LAUNCH();
   return 0;
 }

@@ -317,8 +317,6 @@ bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 // 1 = launched, 0 = not applicable (caller runs the tiled GEMM), < 0 = launch error
 int dfk_wres_try(const dfk_gemm_args& g, hipStream_t s) {
-  static const bool off = getenv("DFK_WRES") && atoi(getenv("DFK_WRES")) == 0;
-  if (off) return 0;
   if (g.dtype != DFK_BF16 || g.a_kmajor || g.c_f32 || g.atomic || g.splitk != 1 || g.rowsum) return 0;
   if (g.nz0 != 1 || g.nz1 != 1 || g.a.conv_cg > 0 || g.b.conv_cg > 0 || g.beta != 0.f) return 0;
   if (g.M < 16384 || g.K % 32 || g.K > 384 || g.N % 4) return 0;

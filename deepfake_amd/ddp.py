@@ -64,15 +64,10 @@ def watchdog_idle(timeout=60.0, exclude=()):
     import time
     _fr_dumps()
     t0 = time.monotonic()
-    polls = 0
     while True:
-        ents = [e for e in fr_entries()
-                if not any(lo < int(e.get("record_id", -1)) <= hi for lo, hi in exclude)]
-        live = [e for e in ents if not e.get("retired", False)]
-        polls += 1
-        if os.environ.get("DFK_DEBUG_WATCHDOG") and (polls == 1 or not live):
-            print(f"[watchdog_idle] poll {polls} t={time.monotonic() - t0:.4f}s entries={len(ents)} live={len(live)} "
-                  f"{[(e.get('profiling_name'), e.get('state')) for e in live[:4]]}", flush=True)
+        live = [e for e in fr_entries()
+                if not e.get("retired", False)
+                and not any(lo < int(e.get("record_id", -1)) <= hi for lo, hi in exclude)]
         if not live:
             return
         if time.monotonic() - t0 > timeout:

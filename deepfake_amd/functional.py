@@ -5,8 +5,6 @@ read through ``compute_weight`` (the bf16 shadow kept by
 deepfake_amd.params.ParamStore, else a per-call cast) and every weight /
 bias gradient is produced in fp32.
 """
-import os
-
 import torch
 
 from . import kernels as K
@@ -359,11 +357,9 @@ class LayerNormFn(torch.autograd.Function):
         x, weight, bias, mean, rstd = ctx.saved_tensors
         dy = dy.contiguous()
         dw, db = grad_sink(weight), grad_sink(bias)
-        if ctx.skip and dskip is not None:   # dx = LN'(dy) + the skip path's gradient, in one pass
-            dx = K.layernorm_bwd(dy, x, compute_weight(weight, x.dtype), mean, rstd, dw, db, drop=ctx.drop,
-                                 addend=_skip_grad_buffer(dskip, x))
-        else:
-            dx = K.layernorm_bwd(dy, x, compute_weight(weight, x.dtype), mean, rstd, dw, db, drop=ctx.drop)
+        # with a skip alias: dx = LN'(dy) + the skip path's gradient, in one pass
+        dx = K.layernorm_bwd(dy, x, compute_weight(weight, x.dtype), mean, rstd, dw, db, drop=ctx.drop,
+                             addend=_skip_grad_buffer(dskip, x) if ctx.skip and dskip is not None else None)
         return dx, grad_done(weight, dw), grad_done(bias, db), None, (dy if ctx.has_res else None), None, None
 
 
@@ -435,26 +431,10 @@ class WindowAttnFn(torch.autograd.Function):
 def window_attention(qkv, rpb, qkv_bias, geo, mask=None, drop=None, dscore=None):
     """drop: attention-probability dropout (bf16 table path only).  dscore: [heads] fp32 buffer the backward adds
     sum dS * score into (SwinV2's logit_scale gradient, consumed and re-zeroed by CosineQKFn's backward; bf16
-    table path without dropout only — see dscore_buffer)."""
+    table path without dropout only; the models pass none: CosineQKFn derives that gradient from q-hat . dq')."""
     if drop is not None and qkv.dtype != torch.bfloat16:
         raise NotImplementedError("attention dropout runs in the bf16 table kernels only (fp32 parity mode: p = 0)")
     return WindowAttnFn.apply(qkv, rpb, qkv_bias, mask, geo, drop, dscore)
-
-
-def dscore_buffer(owner, qkv, heads, drop):
-    """The [heads] fp32 buffer through which the attention backward hands sum dS * score to CosineQKFn's backward
-    (dfk_wattn_bwd_args.dscore), or None where the attention kernel cannot produce it (fp32 parity mode, attention
-    dropout): CosineQKFn then derives the logit_scale gradient from q-hat . dq'.
-    Persistent per module (zeroed once; the consumer re-zeroes it), so a captured step holds no fill for it."""
-    if qkv.dtype != torch.bfloat16 or drop is not None or os.environ.get("DFK_COS_DSCORE", "0") != "1":
-        return None
-    buf = getattr(owner, "_dfk_dscore", None)
-    if buf is None or buf.device != qkv.device or buf.numel() != heads:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("dscore buffer created inside a graph capture (run one eager step first)")
-        buf = torch.zeros(heads, device=qkv.device, dtype=torch.float32)
-        owner._dfk_dscore = buf
-    return buf
 
 
 class DropoutFn(torch.autograd.Function):
@@ -556,6 +536,40 @@ class W2VConv0Fn(torch.autograd.Function):
         return None, grad_done(weight, dw), grad_done(gamma, dg), grad_done(beta, db), None, None
 
 
+def _conv1d_gemm_fwd(x, weight, stride, out, bias=None, act=0, aux=None):
+    """Channels-last Conv1d(Cin->Cout, k, stride) as an implicit GEMM per clip: out[b,t,co] = act(sum_{kk,ci}
+    W[co,ci,kk] x[b, stride*t+kk, ci] + bias) (act 1: gelu, pre-activation -> aux).  Returns the weight operand
+    w2 [Cout, k*Cin]."""
+    B, Tin, Cin = x.shape
+    Cout, _, k = weight.shape
+    Tout = out.shape[1]
+    w2 = weight.detach().permute(0, 2, 1).reshape(Cout, k * Cin).to(x.dtype).contiguous()
+    K.gemm(x, Cin, False, w2, k * Cin, False, Tout, Cout, k * Cin, out, Cout, dtype=K.L.dt(x),
+           bias=compute_weight(bias, x.dtype), act=act, aux=aux, ldaux=Cout if aux is not None else 0, nz=(B, 1),
+           a_bs=(Tin * Cin, 0), c_bs=(Tout * Cout, 0), a_conv=(Cin, stride, 0, Tin))
+    return w2
+
+
+def _conv1d_gemm_bwd(x, w2, dpre, stride, k, need_dx):
+    """(dx or None, dw [Cout, Cin, k] fp32) of _conv1d_gemm_fwd from the pre-activation's gradient dpre: the
+    split-K dW GEMM and one dX GEMM per tap."""
+    B, Tin, Cin = x.shape
+    Tout, Cout = dpre.shape[1:]
+    dt = K.L.dt(x)
+    dw2 = torch.zeros(Cout, k * Cin, device=x.device)
+    tiles = -(-Cout // 128) * -(-(k * Cin) // 128)
+    K.gemm(dpre, Cout, True, x, Cin, True, Cout, k * Cin, Tout, dw2, k * Cin, dtype=dt, c_f32=True, atomic=True,
+           splitk=max(1, min(K.splitk_for(tiles * B, Tout, 128), 16)), nz=(B, 1), a_bs=(Tout * Cout, 0),
+           b_bs=(Tin * Cin, 0), b_conv=(Cin, stride, 0, Tin))
+    dx = None
+    if need_dx:
+        dx = torch.zeros(B, Tin, Cin, device=x.device, dtype=x.dtype)
+        for kk in range(k):  # col2im: tap kk of output t lands on input row stride*t + kk
+            K.gemm(dpre, Cout, False, w2[:, kk * Cin:], k * Cin, True, Tout, Cin, Cout, dx[:, kk:], stride * Cin,
+                   dtype=dt, beta=1.0, nz=(B, 1), a_bs=(Tout * Cout, 0), c_bs=(Tin * Cin, 0))
+    return dx, dw2.view(Cout, k, Cin).permute(0, 2, 1)
+
+
 class ConvGeluFn(torch.autograd.Function):
     """Channels-last Conv1d(Cin->Cout, k, stride s, no bias) + GELU as an
     implicit GEMM (HF modeling_wav2vec2.py:253-272, conv layers 1..6):
@@ -563,38 +577,20 @@ class ConvGeluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, stride):
-        B, Tin, Cin = x.shape
+        B, Tin, _ = x.shape
         Cout, _, k = weight.shape
-        Tout = (Tin - k) // stride + 1
-        dt = x.dtype
-        w2 = weight.detach().permute(0, 2, 1).reshape(Cout, k * Cin).to(dt).contiguous()
-        y = torch.empty(B, Tout, Cout, device=x.device, dtype=dt)
+        y = torch.empty(B, (Tin - k) // stride + 1, Cout, device=x.device, dtype=x.dtype)
         pre = torch.empty_like(y)
-        K.gemm(x, Cin, False, w2, k * Cin, False, Tout, Cout, k * Cin, y, Cout, dtype=K.L.dt(x), act=1, aux=pre,
-               ldaux=Cout, nz=(B, 1), a_bs=(Tin * Cin, 0), c_bs=(Tout * Cout, 0), a_conv=(Cin, stride, 0, Tin))
+        w2 = _conv1d_gemm_fwd(x, weight, stride, y, act=1, aux=pre)
         ctx.save_for_backward(x, w2, pre)
-        ctx.meta = (stride, k, Cin, Cout, Tin, Tout, weight.shape)
+        ctx.meta = (stride, k)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w2, pre = ctx.saved_tensors
-        stride, k, Cin, Cout, Tin, Tout, wshape = ctx.meta
-        B = x.shape[0]
-        dt = K.L.dt(x)
-        dpre = K.gelu_bwd(dy.contiguous(), pre)
-        dw2 = torch.zeros(Cout, k * Cin, device=x.device)
-        tiles = -(-Cout // 128) * -(-(k * Cin) // 128)
-        K.gemm(dpre, Cout, True, x, Cin, True, Cout, k * Cin, Tout, dw2, k * Cin, dtype=dt, c_f32=True, atomic=True,
-               splitk=max(1, min(K.splitk_for(tiles * B, Tout, 128), 16)), nz=(B, 1), a_bs=(Tout * Cout, 0),
-               b_bs=(Tin * Cin, 0), b_conv=(Cin, stride, 0, Tin))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.zeros(B, Tin, Cin, device=x.device, dtype=x.dtype)
-            for kk in range(k):  # col2im: tap kk of output t lands on input row stride*t + kk
-                K.gemm(dpre, Cout, False, w2[:, kk * Cin:], k * Cin, True, Tout, Cin, Cout, dx[:, kk:], stride * Cin,
-                       dtype=dt, beta=1.0, nz=(B, 1), a_bs=(Tout * Cout, 0), c_bs=(Tin * Cin, 0))
-        dw = dw2.view(Cout, k, Cin).permute(0, 2, 1)
+        stride, k = ctx.meta
+        dx, dw = _conv1d_gemm_bwd(x, w2, K.gelu_bwd(dy.contiguous(), pre), stride, k, ctx.needs_input_grad[0])
         return dx, dw, None
 
 
@@ -633,44 +629,26 @@ class ConvLNGeluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, stride, eps):
-        B, Tin, Cin = x.shape
+        B, Tin, _ = x.shape
         Cout, _, k = weight.shape
-        Tout = (Tin - k) // stride + 1
-        dt = x.dtype
-        w2 = weight.detach().permute(0, 2, 1).reshape(Cout, k * Cin).to(dt).contiguous()
-        pre = torch.empty(B, Tout, Cout, device=x.device, dtype=dt)
-        K.gemm(x, Cin, False, w2, k * Cin, False, Tout, Cout, k * Cin, pre, Cout, dtype=K.L.dt(x),
-               bias=compute_weight(bias, dt), nz=(B, 1), a_bs=(Tin * Cin, 0), c_bs=(Tout * Cout, 0),
-               a_conv=(Cin, stride, 0, Tin))
+        pre = torch.empty(B, (Tin - k) // stride + 1, Cout, device=x.device, dtype=x.dtype)
+        w2 = _conv1d_gemm_fwd(x, weight, stride, pre, bias=bias)
         y, stats = K.w2v_ln_gelu_fwd(pre, gamma.detach().float(), beta.detach().float(), eps)
         for i, p in ((2, bias), (3, gamma), (4, beta)):
             if p is not None:
                 grad_use(ctx, i, p)
         ctx.save_for_backward(x, w2, pre, stats, bias, gamma, beta)
-        ctx.meta = (stride, k, Cin, Cout, Tin, Tout)
+        ctx.meta = (stride, k)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w2, pre, stats, bias, gamma, beta = ctx.saved_tensors
-        stride, k, Cin, Cout, Tin, Tout = ctx.meta
-        B = x.shape[0]
-        dt = K.L.dt(x)
+        stride, k = ctx.meta
         dg, dbe = grad_sink(gamma), grad_sink(beta)
         db = grad_sink(bias) if bias is not None else None
         dpre = K.w2v_ln_gelu_bwd(dy.contiguous(), pre, gamma.detach().float(), beta.detach().float(), stats, dg, dbe, db)
-        dw2 = torch.zeros(Cout, k * Cin, device=x.device)
-        tiles = -(-Cout // 128) * -(-(k * Cin) // 128)
-        K.gemm(dpre, Cout, True, x, Cin, True, Cout, k * Cin, Tout, dw2, k * Cin, dtype=dt, c_f32=True, atomic=True,
-               splitk=max(1, min(K.splitk_for(tiles * B, Tout, 128), 16)), nz=(B, 1), a_bs=(Tout * Cout, 0),
-               b_bs=(Tin * Cin, 0), b_conv=(Cin, stride, 0, Tin))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.zeros(B, Tin, Cin, device=x.device, dtype=x.dtype)
-            for kk in range(k):  # col2im: tap kk of output t lands on input row stride*t + kk
-                K.gemm(dpre, Cout, False, w2[:, kk * Cin:], k * Cin, True, Tout, Cin, Cout, dx[:, kk:], stride * Cin,
-                       dtype=dt, beta=1.0, nz=(B, 1), a_bs=(Tout * Cout, 0), c_bs=(Tin * Cin, 0))
-        dw = dw2.view(Cout, k, Cin).permute(0, 2, 1)
+        dx, dw = _conv1d_gemm_bwd(x, w2, dpre, stride, k, ctx.needs_input_grad[0])
         return (dx, dw, grad_done(bias, db) if bias is not None else None, grad_done(gamma, dg), grad_done(beta, dbe),
                 None, None)
 

@@ -6,7 +6,6 @@ Activations are 2-D token-major views ([rows, C], contiguous rows).
 """
 import ctypes
 import math
-import os
 
 import torch
 
@@ -16,7 +15,7 @@ from . import _lib as L
 # dW fastest, but inside the step the other two branch streams fill the chip and fewer splits mean fewer fp32
 # partials (whole-step A/B, C2: 512 / 256 / 128 = 241.7 / 244.8 / 245.3 clips/s, 64: 232.7; C4 Swin-B:
 # 134.1 / 133.1 / 124.3 — 256 holds both; round 4, r4tg: C2 160 / 256 = 257.9 / 256.7, C4 134.1 / 139.2)
-_CU_TARGET_BLOCKS = int(os.environ.get("DFK_DW_TARGET", "256"))
+_CU_TARGET_BLOCKS = 256
 
 
 def _view(t, ld, bs0=0, bs1=0, conv=None):
@@ -28,23 +27,17 @@ def _view(t, ld, bs0=0, bs1=0, conv=None):
     return v
 
 
-def gemm(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, *, dtype, c_f32=False, bias=None,
-         residual=None, ldr=0, aux=None, ldaux=0, act=0, beta=0.0, atomic=False, splitk=1,
-         nz=(1, 1), a_bs=(0, 0), b_bs=(0, 0), c_bs=(0, 0), r_bs=(0, 0), a_conv=None, b_conv=None, bias_bs1=0,
-         rowsum=None, drop=None, alpha=0.0):
-    """Raw dfk_gemm.  a/b/c are tensors (base pointers); see include/dfk.h.  drop: rng.Drop spec of the
-    output's dropout / DropPath (applied before the residual add)."""
-    _gemm_launch(_gemm_args(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, dtype=dtype, c_f32=c_f32, bias=bias,
-                            residual=residual, ldr=ldr, aux=aux, ldaux=ldaux, act=act, beta=beta, atomic=atomic,
-                            splitk=splitk, nz=nz, a_bs=a_bs, b_bs=b_bs, c_bs=c_bs, r_bs=r_bs, a_conv=a_conv,
-                            b_conv=b_conv, bias_bs1=bias_bs1, rowsum=rowsum, drop=drop, alpha=alpha), c)
+def gemm(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, **kw):
+    """Raw dfk_gemm.  a/b/c are tensors (base pointers); the keywords are _gemm_args'; see include/dfk.h."""
+    _gemm_launch(_gemm_args(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, **kw), c)
 
 
 def _gemm_args(a, a_ld, a_kmajor, b, b_ld, b_kmajor, M, N, K, c, ldc, *, dtype, c_f32=False, bias=None,
                residual=None, ldr=0, aux=None, ldaux=0, act=0, beta=0.0, atomic=False, splitk=1,
                nz=(1, 1), a_bs=(0, 0), b_bs=(0, 0), c_bs=(0, 0), r_bs=(0, 0), a_conv=None, b_conv=None, bias_bs1=0,
                rowsum=None, drop=None, alpha=0.0):
-    """The dfk_gemm_args of gemm()'s arguments (no workspace yet)."""
+    """The dfk_gemm_args of gemm()'s arguments (no workspace yet).  drop: rng.Drop spec of the output's dropout /
+    DropPath (applied before the residual add)."""
     g = L.GemmArgs()
     if drop is not None:
         g.drop = L.drop(drop, c.device)
@@ -195,13 +188,12 @@ def linear_dx(dy, w, out=None, act=0, aux=None, beta=0.0, drop=None, residual=No
     return out
 
 
-_DX_BLAS = os.environ.get("DFK_DX_BLAS", "1") == "1"   # plain small-M dX products on hipBLASLt (DFK_DX_BLAS=0: dfk_gemm)
-_DX_BLAS_MAX_M = int(os.environ.get("DFK_DX_BLAS_MAX_M", "131072"))
-_DW_MIN_K = int(os.environ.get("DFK_DW_MINK", "512"))   # tokens per split of a weight-gradient GEMM (tuning)
-_DW_UNSPLIT64 = int(os.environ.get("DFK_DW_UNSPLIT64", "384"))   # 64x64 tiles from which dW runs unsplit (r5o: the
-# 256-tile SwinV2 stage-3 fc1 / fc2 dW 22 -> 19, 21 -> 19 us on split 128x128 tiles; w2v (432-576 tiles) flat)
-_DW_XCD = int(os.environ.get("DFK_DW_XCD", "1"))   # split counts rounded to multiples of 8 (XCD grouping; A/B knob)
-_DW_SLAB = os.environ.get("DFK_DW_SLAB", "0") == "1"   # fp32 split slabs + one reduce instead of split atomics (A/B knob)
+_DX_BLAS = True             # plain small-M dX products on hipBLASLt (False: dfk_gemm; r6aa)
+_DX_BLAS_MAX_M = 131072
+_DW_MIN_K = 512             # tokens per split of a weight-gradient GEMM
+_DW_UNSPLIT64 = 384         # 64x64 tiles from which dW runs unsplit (r5o: the 256-tile SwinV2 stage-3 fc1 / fc2
+# dW 22 -> 19, 21 -> 19 us on split 128x128 tiles; w2v (432-576 tiles) flat)
+_DW_SLAB = False            # fp32 split slabs + one reduce instead of split atomics (tests set it; r5y: atomics win)
 
 
 def splitk_for(tiles, K, min_k=None):
@@ -210,8 +202,8 @@ def splitk_for(tiles, K, min_k=None):
 
 
 # Grouped weight gradients (dfk_gemm_dw_group): the small dW problems of one block are queued per stream and issued
-# as one launch per tile shape at dw_flush().  DFK_DW_GROUP=0 / dw_group_policy(0): every problem launches at once.
-_DW_GROUP = [int(os.environ.get("DFK_DW_GROUP", "1"))]
+# as one launch per tile shape at dw_flush().  dw_group_policy(0): every problem launches at once.
+_DW_GROUP = [1]
 _DW_GROUP_MAX = 8                       # pending problems at which a queue flushes itself (one native chunk)
 _DW_GROUP_BLOCKS = 768                  # a problem is deferred when its own grid is below 3 workgroups per CU ...
 _DW_GROUP_BYTES = 32 << 20              # ... and its operands (dy and x) take at most this many bytes
@@ -300,26 +292,27 @@ def linear_dw(dy, x, dw, db=None, defer=False, done=None):
     return dw
 
 
+def dw_plan(M, N, K):
+    """(splitk, atomic, workgroups) of the weight-gradient GEMM dw[N, K] += dy[M, N]^T x[M, K]: integers only."""
+    if math.ceil(N / 64) * math.ceil(K / 64) >= _DW_UNSPLIT64:
+        return 1, False, math.ceil(N / 64) * math.ceil(K / 64)
+    tiles = math.ceil(N / 128) * math.ceil(K / 128)
+    s = splitk_for(tiles, M)
+    # fp32 partial bytes (splits x N x K x 4) kept to a quarter of the operand bytes read, except that small
+    # grids keep up to 8 splits for parallelism (C2 sweep: mel1.fc1 [25088]x512x128 98 -> 30 splits, 42 -> 28 us)
+    s = max(1, min(s, max(8, M * (N + K) // (8 * N * K))))
+    if tiles > 1 and s >= 16:
+        s -= s % 8   # a multiple of 8 splits: the kernel puts each split's tiles on one XCD (shared operand in L2)
+    return s, s > 1 and not _DW_SLAB, tiles * s   # _DW_SLAB: fp32 split slabs + one reduce pass, no atomics
+
+
 def _dw_args(dy, x, dw, db):
-    """(dfk_gemm_args, workgroups) of linear_dw's problem: the split plan of the weight-gradient GEMM."""
+    """(dfk_gemm_args, workgroups) of linear_dw's problem."""
     M, N = dy.shape
     K = x.shape[1]
-    if math.ceil(N / 64) * math.ceil(K / 64) >= _DW_UNSPLIT64:
-        blocks = math.ceil(N / 64) * math.ceil(K / 64)
-        g = _gemm_args(dy, dy.stride(0), True, x, x.stride(0), True, N, K, M, dw, dw.stride(0), dtype=L.dt(dy),
-                       c_f32=True, beta=1.0, rowsum=db)
-    else:
-        tiles = math.ceil(N / 128) * math.ceil(K / 128)
-        s = splitk_for(tiles, M)
-        # fp32 partial bytes (splits x N x K x 4) kept to a quarter of the operand bytes read, except that small
-        # grids keep up to 8 splits for parallelism (C2 sweep: mel1.fc1 [25088]x512x128 98 -> 30 splits, 42 -> 28 us)
-        s = max(1, min(s, max(8, M * (N + K) // (8 * N * K))))
-        if _DW_XCD and tiles > 1 and s >= 16:
-            s -= s % 8   # a multiple of 8 splits: the kernel puts each split's tiles on one XCD (shared operand in L2)
-        slab = s > 1 and _DW_SLAB   # A/B: fp32 split slabs + one reduce pass instead of the splits' fp32 atomics
-        blocks = tiles * s
-        g = _gemm_args(dy, dy.stride(0), True, x, x.stride(0), True, N, K, M, dw, dw.stride(0), dtype=L.dt(dy),
-                       c_f32=True, atomic=s > 1 and not slab, beta=1.0, splitk=s, rowsum=db)
+    s, atomic, blocks = dw_plan(M, N, K)
+    g = _gemm_args(dy, dy.stride(0), True, x, x.stride(0), True, N, K, M, dw, dw.stride(0), dtype=L.dt(dy),
+                   c_f32=True, atomic=atomic, beta=1.0, splitk=s, rowsum=db)
     return g, blocks
 
 
@@ -343,30 +336,21 @@ def layernorm_fwd(x, w, b, eps=1e-5, out=None, residual=None, drop=None):
     return out, mean, rstd
 
 
-# LayerNorms of <= 4096 rows: at most _LN_SMALL workgroups with atomic dw/db partials (layernorm.hip bwd_blocks)
-_LN_SMALL = int(os.environ.get("DFK_LN_SMALL", "128"))
-_LN_SMALL_ROWS = 4096
-
-
-def _ln_bwd_blocks(rows, C):
-    """Workgroups of ln_bwd (layernorm.hip bwd_blocks)."""
-    nv = C // 8
-    lanes = 16 if nv <= 16 else (32 if nv <= 32 else 64)
-    return min(2048, -(-rows // (4 * (64 // lanes))))
+_LN_SMALL_ROWS = 4096   # layernorm.hip kLnSmallRows: up to here ln_bwd runs at most 128 workgroups, atomic dw/db
 
 
 def layernorm_bwd(dy, x, w, mean, rstd, dw, db, dx=None, accumulate=False, slab_partials=None, drop=None,
                   addend=None):
     """dx (+)= LN backward (+ addend [rows, C] of x's dtype, read: the skip path's gradient summed in the same
-    pass without writing into it); dw / db (fp32) += the affine gradients.  slab_partials (default: from 64
-    workgroups up) writes each workgroup's dw/db partial to a slab summed by a column pass instead of adding
+    pass without writing into it); dw / db (fp32) += the affine gradients.  slab_partials (default: above
+    _LN_SMALL_ROWS rows) writes each workgroup's dw/db partial to a slab summed by a column pass instead of adding
     it atomically: hundreds of workgroups adding into the same C addresses serialise on a few L2 channels
     (the 1568 x 512 SwinV2 / wav2vec2 LNs ran 20 us, the 401k x 96 stage-1 LN 116 us)."""
     rows, C = x.shape
     if dx is None:
         dx = torch.empty_like(x)
     if slab_partials is None:
-        slab_partials = _ln_bwd_blocks(rows, C) >= 64 and not (_LN_SMALL > 0 and rows <= _LN_SMALL_ROWS)
+        slab_partials = rows > _LN_SMALL_ROWS
     ws = None
     if slab_partials and (dw is not None or db is not None):   # per-workgroup dw/db partials + column sums
         ws = torch.empty(max(L.lib().dfk_layernorm_bwd_workspace(rows, C) // 4, 1), device=x.device,

@@ -5,8 +5,6 @@ The head runs on [B, <=1536] features: its Linear layers are the MFMA GEMM
 statistics, momentum 0.08) and sigmoid are latency-trivial torch ops.
 Extractor features arrive as fp32 [B, dim] whatever the trunk compute dtype.
 """
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -63,10 +61,9 @@ class FusionModel(nn.Module):
 
     def branch_streams(self):
         if not hasattr(self, "_streams"):
-            # A/B knob: HIP stream priorities of the video / mel / waveform branches, e.g. "-1,0,0" (lower = higher)
-            pr = os.environ.get("DFK_BRANCH_PRIO")
-            ps = [int(v) for v in pr.split(",")] if pr else [0, 0, 0]
-            self._streams = [torch.cuda.Stream(priority=p) for p in ps]
+            # video / mel / waveform, all of priority 0: raising one branch lost the step A/B twice
+            # (profiles/step/r3o_branch_priority_rejected.txt, r6r_branch_stream_priority_rejected.txt)
+            self._streams = [torch.cuda.Stream(priority=0) for _ in range(3)]
         return self._streams
 
     def join_branches(self):

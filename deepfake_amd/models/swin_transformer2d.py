@@ -10,7 +10,6 @@ normalised, q scaled by exp(clamp(logit_scale))) + window attention with the
 x + LN(attn(x)), x + LN(mlp(x)) (:288-291).
 """
 import math
-import os
 
 import numpy as np
 import torch
@@ -118,14 +117,13 @@ class WindowAttention(nn.Module):
         else:
             qkv = Fn.linear(x2d, self.qkv.weight)
         ad = self.attn_drop.spec() if self.attn_drop is not None and self.training else None
-        # logit_scale's gradient: sum dS * score taken in fp32 inside the attention backward (dfk_wattn_bwd_args
-        # .dscore), handed to the cosine backward through a per-module buffer
-        dsc = Fn.dscore_buffer(self, qkv, self.num_heads, ad) if self.logit_scale.requires_grad else None
-        qkv = Fn.CosineQKFn.apply(qkv, self.logit_scale, self.num_heads, hd, math.log(1. / 0.01), dsc)
+        # logit_scale's gradient comes from q-hat . dq' in the cosine backward (no dscore from the attention backward:
+        # DESIGN.md "SwinV2 logit_scale gradient")
+        qkv = Fn.CosineQKFn.apply(qkv, self.logit_scale, self.num_heads, hd, math.log(1. / 0.01))
         geo = (dims, (1, ws, ws), (1, self.window_size[0], self.window_size[1]), (0, shift, shift),
                self.num_heads, hd, 1.0)
         tab = self._cpb if getattr(self, "_cpb", None) is not None else self.bias_table()
-        out = Fn.window_attention(qkv, tab, None, geo, drop=ad, dscore=dsc)
+        out = Fn.window_attention(qkv, tab, None, geo, drop=ad)
         return (out, xs) if skip else out
 
 
@@ -298,7 +296,7 @@ class SwinTransformerV2(nn.Module):
         # every block's CPB table in one launch each way (parameters only; Fn.cpb_tables), handed to the blocks
         # for this forward only
         attns = [blk.attn for layer in self.layers for blk in layer.blocks]
-        if x.is_cuda and os.environ.get("DFK_CPB_MANY", "1") != "0":
+        if x.is_cuda:
             for a, t in zip(attns, Fn.cpb_tables(attns)):
                 a._cpb = t
         try:

@@ -29,7 +29,6 @@ parameters (as torch's SGD skips grad=None).  config.deterministic() turns all
 of them off (the parity setting, Q12).
 """
 import json
-import os
 
 import torch
 import torch.nn as nn
@@ -171,16 +170,15 @@ class Wav2Vec2PositionalConvEmbedding(nn.Module):
 
     def weight(self):
         """weight_norm(dim=2): g * v / ||v|| with the norm over dims (0, 1) — same parameters and state_dict
-        keys as the parametrization, composed from plain reductions (torch's dim=2 weight-norm kernels take
-        ~0.45 ms each way on this [768, 48, 128] shape)."""
+        keys as the parametrization, composed from plain reductions.  The tests' reference of the positional
+        conv reads it; the model's path is add_to() (the torch route through this and Fn.PosConvFn lost the step
+        A/B, profiles/step/r6x_posconv_weightnorm.txt)."""
         p = self.conv.parametrizations.weight
         g, v = p.original0, p.original1
         return v * (g / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt())
 
     def add_to(self, x):
         """x + pos_conv(x) fused (HF/:689-690), the weight norm inside the op (Fn.PosConvWNFn)."""
-        if os.environ.get("DFK_POSCONV_WN", "1") == "0":   # A/B: torch weight-norm ops + PosConvFn
-            return Fn.PosConvFn.apply(x, self.weight(), self.conv.bias, self.groups)
         p = self.conv.parametrizations.weight
         return Fn.PosConvWNFn.apply(x, p.original0, p.original1, self.conv.bias, self.groups)
 

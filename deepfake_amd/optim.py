@@ -20,15 +20,15 @@ per quad by the dfk_*_step_runs_groups kernels through a byte map of the store, 
 """
 import contextlib
 import math
-import os
 
 import torch
 
 from . import kernels as K
 
 
-# DFK_SGD_RUNS=0: one dfk_sgd_step launch per run (A/B); default: every run in one dfk_sgd_step_runs launch
-_RUNS = os.environ.get("DFK_SGD_RUNS", "1") != "0"
+# every run in one dfk_sgd_step_runs launch (profiles/step/r6j_sgd_one_launch.txt); False (tests set it): one
+# dfk_sgd_step launch per run
+_RUNS = True
 
 
 NO_DECAY_KEYWORDS = ("relative_position_bias_table", "absolute_pos_embed", "cpb_mlp", "logit_scale")
@@ -182,12 +182,12 @@ class FusedSGD(_Fused):
     def step(self, first=None, grad_scale=1.0, grad_bf16=None):
         """One SGD step over the parameters that received a gradient (torch skips grad=None:
         no weight decay and no momentum for them): every contiguous run in one dfk_sgd_step_runs launch (one
-        dfk_sgd_step per run beyond 64 runs, or with DFK_SGD_RUNS=0).
+        dfk_sgd_step per run beyond 64 runs, or with _RUNS off).
         grad_scale / grad_bf16: the data-parallel fold of GradBucketer.finish(fold=True) — the gradient is the
         all-reduced sum (in the fp32 buffer, or in the bf16 bucket copy) times 1 / world.
         With groups (ParamGroups): the same runs through dfk_sgd_step_runs_groups, 64 per launch, each quad taking
         its group's lr multiplier and weight decay (the constructor's weight_decay is not read); the norm of a
-        clipped step is over all groups; DFK_SGD_RUNS=0 is ignored (the groups kernels have no one-run form)."""
+        clipped step is over all groups; _RUNS is ignored (the groups kernels have no one-run form)."""
         st = self.store
         gates = {id(g): g for g in st.gate if g is not None}
         gkey = [id(g) if g is not None else None for g in st.gate]
@@ -292,8 +292,8 @@ class FusedAdamW(_Fused):
                                          self.groups.group_map, self.groups.group_hyper, grad_scale=grad_scale,
                                          grad_bf16=grad_bf16, **ck)
             return
-        # DFK_SGD_RUNS=0 selects the per-run launches only for a clipped step (A/B of the _clip twins): without
-        # clipping FusedAdamW has never read the variable, and its launches stay what they were
+        # _RUNS off selects the per-run launches only for a clipped step (the tests of the _clip twins): without
+        # clipping FusedAdamW has never read it, and its launches stay what they were
         if (_RUNS or not ck) and len(runs) <= K.SGD_MAX_RUNS:
             K.adamw_step_runs(st.flat, st.grad, self.exp_avg, self.exp_avg_sq, st.shadow,
                               [(s, e, self.gates[c], c) for s, e, c in runs], b1, b2, self.eps, self.weight_decay,

@@ -207,12 +207,10 @@ class TrainStep:
         if not bucketer.bn_buffers:
             bucketer.track_batchnorm(model)
 
-    def _fwd_bwd(self, feature, label, scale=1.0, before_backward=None):
+    def _fwd_bwd(self, feature, label, scale=1.0):
         rng.advance(self.store.flat.device)   # fresh dropout / DropPath / LayerDrop / SpecAugment draws
         prob = self.model(feature)
         loss = self.lossF(prob.float().reshape(-1), label.float().reshape(-1))
-        if before_backward is not None:
-            before_backward()
         (loss * scale if scale != 1.0 else loss).backward()
         # deferred weight gradients left in a trunk's queue go out on that trunk's stream before the streams join
         # (the backward pass's own end-of-pass flush has normally emptied the queues already)
@@ -372,27 +370,16 @@ class TrainStep:
 
     def _step_body(self, static_in, static_label, accum):
         """The optimizer step's graph body: (zeroing,) BN broadcast, fwd + bwd, all-reduces, optimizer."""
-        # where the step graph zeroes the gradients (A/B): 0 at the start, 1 after the forward, 2 on a side stream
-        # beside the forward (joined before the backward)
-        zmode = int(os.environ.get("DFK_ZERO_MODE", "0")) if accum == 1 else 0
-
         def body(overlap, bn):
-            join = None
             if accum == 1:
-                if zmode == 0:
-                    self.store.grad.zero_()
-                elif zmode == 2:
-                    zs = self._side_stream()
-                    zs.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(zs):
-                        self.store.grad.zero_()
-                    join = lambda: torch.cuda.current_stream().wait_stream(zs)   # noqa: E731
-                else:
-                    join = self.store.grad.zero_
+                # the gradients are zeroed at the start of the graph: after the forward, or on a side stream beside it,
+                # the memset's traffic lands on whatever runs next and the step is no faster (DESIGN.md "Conv3D
+                # in-step: the cause found")
+                self.store.grad.zero_()
                 self.store.zero_gates()
                 if bn:
                     self.bucketer.broadcast_bn()
-            l2, p2 = self._fwd_bwd(tuple(static_in), static_label, 1.0 / accum, before_backward=join)
+            l2, p2 = self._fwd_bwd(tuple(static_in), static_label, 1.0 / accum)
             fold = self._fold()
             if overlap:
                 fa = self.bucketer.finish(fold=fold)   # flush unused buckets, join the comm stream
@@ -406,11 +393,6 @@ class TrainStep:
                 self.store.zero_gates()
             return l2.detach(), p2.detach()
         return body
-
-    def _side_stream(self):
-        if getattr(self, "_zstream", None) is None:
-            self._zstream = torch.cuda.Stream()
-        return self._zstream
 
     def _fallback(self, err):
         self.graph_mode = False
@@ -426,8 +408,6 @@ class TrainStep:
         all ranks run eagerly."""
         self.static = [[x.clone() for x in feature], label.clone(), None, None]
         forms = self.FORMS if self.bucketer.enabled else ((False, False),)
-        if os.environ.get("DFK_CAPTURE_OVERLAP") == "0":   # probes: only the one-pass forms
-            forms = tuple(f for f in forms if not f[0])
         g, outs, form = self._graph(self._step_body(self.static[0], self.static[1], 1), forms)
         if g is None:
             return self._fallback(outs)

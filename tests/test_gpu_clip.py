@@ -518,7 +518,7 @@ def test_optimizer_with_more_than_64_runs(kind):
 
 @pytest.mark.parametrize("kind", ["sgd", "adamw"])
 def test_per_run_launches_of_the_optimizer_equal_the_runs_launch(kind, monkeypatch):
-    """DFK_SGD_RUNS=0 (optim._RUNS False): a clipped step goes through one _clip launch per run and gives the bits
+    """optim._RUNS False: a clipped step goes through one _clip launch per run and gives the bits
     of the one-launch form."""
     from deepfake_amd import optim
     gen = torch.Generator().manual_seed(12)

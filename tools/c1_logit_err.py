@@ -1,6 +1,6 @@
 """C1 bf16 training step: the SwinV2 logit_scale gradient norms against the reference's fp32 step and the
 reference's own bf16 error (tests/golden/fused_c1.npz gn:*, fused_c1_grads.npz ea:*), plus the worst tensor
-overall.  A/B: DFK_COS_DSCORE=0 (q-hat . dq' in the cosine backward)."""
+overall (the gradient comes from q-hat . dq' in the cosine backward)."""
 import os
 import sys
 
@@ -22,7 +22,6 @@ m.train()
 p = m((video.cuda(), mel.cuda(), wave.cuda()))
 torch.nn.BCELoss()(p.float(), label.cuda()).backward()
 names = dict(m.named_parameters())
-tag = f"dscore={os.environ.get('DFK_COS_DSCORE', '1')}"
 worst = (None, 0.0, 0.0)
 for k in keys(fx, "gn:"):
     n = k[3:]
@@ -30,7 +29,7 @@ for k in keys(fx, "gn:"):
     e = float(ea.get("ea:" + n, 0.0))
     r = abs(got - ref) / max(ref, 1e-12)
     if "logit_scale" in n:
-        print(f"{tag} {n}: rel {r:.4f}  ref-bf16 {e:.4f}  ratio {r / max(e, 1e-9):.2f}")
+        print(f"{n}: rel {r:.4f}  ref-bf16 {e:.4f}  ratio {r / max(e, 1e-9):.2f}")
     if ref > 1e-4 and r / max(2e-2, 6 * e) > worst[2]:
         worst = (n, r, r / max(2e-2, 6 * e))
-print(f"{tag} worst tensor vs its gate: {worst}")
+print(f"worst tensor vs its gate: {worst}")

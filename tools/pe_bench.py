@@ -1,5 +1,4 @@
-"""Conv3D patch-embed forward (dfk_patch_embed_fwd) cold timing at C2 (B=8), as bench.py's roofline_conv3d.
-Tuning knobs via env: DFK_PE_PERCU (workgroups per CU), DFK_PE_DEPTH (rows of clip loads in flight)."""
+"""Conv3D patch-embed forward (dfk_patch_embed_fwd) cold timing at C2 (B=8), as bench.py's roofline_conv3d."""
 import os
 import sys
 
@@ -8,4 +7,4 @@ import bench  # noqa: E402
 from deepfake_amd.models.fused import CONFIGS  # noqa: E402
 
 r = bench.conv3d_roofline(CONFIGS["c2"], 8, 50)
-print(os.environ.get("DFK_PE_PERCU", "-"), os.environ.get("DFK_PE_DEPTH", "-"), r["avg_launch_ms"], r["frac"], flush=True)
+print(r["avg_launch_ms"], r["frac"], flush=True)
