@@ -12,6 +12,9 @@
                            samples wav2vec2 gets), resampled and turned into the mel image on the GPU
   --audio_seconds_min      shortest synthetic clip (seconds): clips of unequal length, each mel image built from its
                            clip's own length on the GPU (default: one fixed length)
+  --paudio_lengths         waveform slot with per-clip lengths (layer-norm --w2v_config only): each clip normalised
+                           over its own samples, its padding masked in every wav2vec2 attention layer and left out of
+                           the pooled feature; the padded waveform keeps the configuration's fixed length
   --bucket_mb              gradient all-reduce bucket size
   --deterministic          dropout / DropPath / SpecAugment / LayerDrop off (the parity setting, Q12)
   --optimizer {sgd,adamw}  the reference's SGD(momentum 0.9) (default) or the AdamW it keeps beside it
@@ -97,6 +100,9 @@ def build_parser():
                         help='shortest clip in seconds: every clip draws its own audio length between this and the '
                              "configuration's (unequal clips per batch; the waveform mel sources then build each "
                              "image from its clip's own length).  Default: every clip has the configuration's length")
+    parser.add_argument('--paudio_lengths', action='store_true',
+                        help="waveform slot: pass every clip's own length to wav2vec2 (per-clip normalisation, key "
+                             'padding mask, pooling over the clip\'s frames); needs a layer-norm --w2v_config')
     parser.add_argument('--augment', action='store_true')
     parser.add_argument('--bucket_dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     parser.add_argument('--bucket_mb', type=float, default=64.0)

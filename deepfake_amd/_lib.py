@@ -53,7 +53,7 @@ class WattnArgs(C.Structure):
                 ("fd", C.c_int32), ("fh", C.c_int32), ("fw", C.c_int32),
                 ("sd", C.c_int32), ("sh", C.c_int32), ("sw", C.c_int32),
                 ("heads", C.c_int32), ("hd", C.c_int32), ("dtype", C.c_int32), ("scale", C.c_float),
-                ("tab", C.c_void_p), ("drop", Drop)]
+                ("tab", C.c_void_p), ("drop", Drop), ("klen", C.c_void_p)]
 
 
 class WattnBwdArgs(C.Structure):
@@ -175,8 +175,14 @@ SIGNATURES = {
     "dfk_layer_select": [_VP, _VP, _VP, _VP, _VP, C.c_int64, _VP],
     "dfk_spec_augment_fwd": [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _F, _I32, _I32, C.POINTER(Drop), C.c_int, _VP],
     "dfk_spec_augment_bwd": [_VP, _VP, _VP, _VP, _I32, _I32, _I32, C.c_int, _VP],
+    "dfk_spec_augment_ragged_fwd": [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _F, _I32, _I32, C.POINTER(Drop), C.c_int,
+                                    _VP],
+    "dfk_row_mask": [_VP, _VP, _VP, _I32, _I32, _I32, C.c_int, _VP],
+    "dfk_rowmean_ragged_fwd": [_VP, _VP, _VP, _I32, _I32, _I32, C.c_int, _VP],
+    "dfk_rowmean_ragged_bwd": [_VP, _VP, _VP, _I32, _I32, _I32, C.c_int, _VP],
     "dfk_frame_normalize": [_VP, _VP, _I64, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _VP],
     "dfk_wave_normalize": [_VP, _VP, _I64, _I64, _F, _VP],
+    "dfk_wave_normalize_ragged": [_VP, _VP, _VP, _I64, _I64, _F, _VP],
     "dfk_patch_embed_fwd": [C.POINTER(PatchEmbedArgs), _VP],
     "dfk_patch_embed_bwd": [C.POINTER(PatchEmbedArgs), _VP, _VP],
 }

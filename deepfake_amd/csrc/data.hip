@@ -7,7 +7,9 @@
 //    HBM-bound: 1 byte read + 4 bytes written per element.
 //  * waveform normalisation — Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm (transformers
 //    feature_extraction_wav2vec2.py:94-95, called at src/trainer.py:258): each (zero-padded, Q13) row
-//    y = (x - mean) / sqrt(var + 1e-7), one workgroup per clip, fp32 two-pass statistics.
+//    y = (x - mean) / sqrt(var + 1e-7), one workgroup per clip, fp32 two-pass statistics.  The ragged form
+//    (the same function with an attention mask, :88-93) takes the statistics over the clip's own samples and
+//    writes zeros behind them, without reading the padding.
 #include "common.h"
 
 namespace {
@@ -49,22 +51,25 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return t;
 }
 
-__global__ __launch_bounds__(1024) void wave_norm_kernel(const float* __restrict__ x, float* __restrict__ y, long S,
-                                                         float eps) {
+// len == nullptr: the whole row; else n = clamp(len[b], 1, S) samples, zeros behind them (x there is not read)
+__global__ __launch_bounds__(1024) void wave_norm_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                         const int64_t* __restrict__ len, long S, float eps) {
   __shared__ float red[16];
   const float* xr = x + (long)blockIdx.x * S;
   float* yr = y + (long)blockIdx.x * S;
+  const long n = len ? (long)min(max(len[blockIdx.x], (int64_t)1), (int64_t)S) : S;
   float s = 0.f;
-  for (long i = threadIdx.x; i < S; i += blockDim.x) s += xr[i];
-  const float mean = block_sum(s, red) / (float)S;
+  for (long i = threadIdx.x; i < n; i += blockDim.x) s += xr[i];
+  const float mean = block_sum(s, red) / (float)n;
   float q = 0.f;
-  for (long i = threadIdx.x; i < S; i += blockDim.x) {
+  for (long i = threadIdx.x; i < n; i += blockDim.x) {
     const float d = xr[i] - mean;
     q += d * d;
   }
-  const float var = block_sum(q, red) / (float)S;
+  const float var = block_sum(q, red) / (float)n;
   const float inv = 1.f / sqrtf(var + eps);
-  for (long i = threadIdx.x; i < S; i += blockDim.x) yr[i] = (xr[i] - mean) * inv;
+  for (long i = threadIdx.x; i < n; i += blockDim.x) yr[i] = (xr[i] - mean) * inv;
+  for (long i = n + threadIdx.x; i < S; i += blockDim.x) yr[i] = 0.f;
 }
 
 }  // namespace
@@ -85,7 +90,17 @@ extern "C" int dfk_frame_normalize(const uint8_t* src, float* dst, int64_t frame
 extern "C" int dfk_wave_normalize(const float* x, float* y, int64_t B, int64_t S, float eps, hipStream_t s) {
   if (!x || !y || B < 0 || S <= 0) return DFK_EINVAL;
   if (B == 0) return 0;
-  hipLaunchKernelGGL(wave_norm_kernel, dim3((unsigned)B), dim3(1024), 0, s, x, y, (long)S, eps);
+  hipLaunchKernelGGL(wave_norm_kernel, dim3((unsigned)B), dim3(1024), 0, s, x, y, (const int64_t*)nullptr, (long)S,
+                     eps);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_wave_normalize_ragged(const float* x, float* y, const int64_t* len, int64_t B, int64_t S, float eps,
+                                         hipStream_t s) {
+  if (!x || !y || !len || B < 0 || S <= 0) return DFK_EINVAL;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(wave_norm_kernel, dim3((unsigned)B), dim3(1024), 0, s, x, y, len, (long)S, eps);
   DFK_CHECK_LAUNCH();
   return 0;
 }

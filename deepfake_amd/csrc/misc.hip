@@ -130,6 +130,56 @@ __global__ __launch_bounds__(256) void rowmean_kernel(const T* __restrict__ x, T
     stf<TO>(out + (long)g * C + c, ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])) / R);
 }
 
+// Padded batches (per-clip frame counts flen, device int64 [B]; Tb = clamp(flen[b], 1, T)).
+__device__ __forceinline__ int frames_of(const int64_t* flen, int b, int T) {
+  return (int)min(max(flen[b], (int64_t)1), (int64_t)T);
+}
+
+// y[b][t][:] = t < Tb ? x[b][t][:] : 0 as a select on 16-B vectors (rows past Tb are not read); cv vectors per row
+__global__ __launch_bounds__(256) void row_mask_kernel(const uint4* __restrict__ x, uint4* __restrict__ y,
+                                                       const int64_t* __restrict__ flen, int T, int cv, long nv) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nv) return;
+  const long row = i / cv;
+  const int b = (int)(row / T), t = (int)(row % T);
+  y[i] = t < frames_of(flen, b, T) ? x[i] : make_uint4(0, 0, 0, 0);
+}
+
+// out[b][c] = mean over t < Tb of x[b][t][c]: rowmean_kernel's layout with the clip's own row count
+template <typename T>
+__global__ __launch_bounds__(256) void rowmean_ragged_kernel(const T* __restrict__ x, float* __restrict__ out,
+                                                             const int64_t* __restrict__ flen, int Tn, int C) {
+  __shared__ float red[4][64];
+  const int g = blockIdx.y, lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  const bool ok = c < C;
+  const int R = frames_of(flen, g, Tn);
+  const T* p = x + (long)g * Tn * C + (ok ? c : 0);
+  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int r = ph;
+  for (; r + 28 < R; r += 32)
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s[u] += ldf<T>(p + (long)(r + 4 * u) * C);
+  for (; r < R; r += 4) s[0] += ldf<T>(p + (long)r * C);
+  red[ph][lane] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+  __syncthreads();
+  if (ph == 0 && ok) out[(long)g * C + c] = ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])) / R;
+}
+
+// dx[b][t][c] = t < Tb ? dy[b][c] / Tb : 0
+template <typename T>
+__global__ __launch_bounds__(256) void rowmean_ragged_bwd_kernel(const float* __restrict__ dy, T* __restrict__ dx,
+                                                                 const int64_t* __restrict__ flen, int Tn, int C,
+                                                                 long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  const long row = i / C;
+  const int b = (int)(row / Tn), t = (int)(row % Tn);
+  const int R = frames_of(flen, b, Tn);
+  stf<T>(dx + i, t < R ? dy[(long)b * C + c] / R : 0.f);
+}
+
 template <typename T>
 __global__ void gelu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ pre, T* __restrict__ dx, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -349,6 +399,46 @@ extern "C" int dfk_rowmean(const void* x, void* out, int groups, int R, int C, i
   } else {
     hipLaunchKernelGGL((rowmean_kernel<float, float>), grid, dim3(256), 0, s, (const float*)x, (float*)out, R, C);
   }
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_row_mask(const void* x, void* y, const int64_t* flen, int32_t B, int32_t T, int32_t C, int dtype,
+                            hipStream_t s) {
+  const int vec = dtype == DFK_BF16 ? 8 : 4;
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (!x || !y || !flen || C <= 0 || C % vec || !al(x) || !al(y)) return DFK_EINVAL;
+  if (B <= 0 || T <= 0) return 0;
+  const long nv = (long)B * T * (C / vec);
+  hipLaunchKernelGGL(row_mask_kernel, dim3((unsigned)dfk_cdiv(nv, 256)), dim3(256), 0, s, (const uint4*)x, (uint4*)y,
+                     flen, (int)T, (int)(C / vec), nv);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_rowmean_ragged_fwd(const void* x, float* out, const int64_t* flen, int32_t B, int32_t T, int32_t C,
+                                      int dtype, hipStream_t s) {
+  if (!x || !out || !flen || T <= 0 || C <= 0) return DFK_EINVAL;
+  if (B <= 0) return 0;
+  const dim3 grid(dfk_cdiv(C, 64), B);
+  if (dtype == DFK_BF16)
+    hipLaunchKernelGGL(rowmean_ragged_kernel<bf16raw>, grid, dim3(256), 0, s, (const bf16raw*)x, out, flen, (int)T, (int)C);
+  else
+    hipLaunchKernelGGL(rowmean_ragged_kernel<float>, grid, dim3(256), 0, s, (const float*)x, out, flen, (int)T, (int)C);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_rowmean_ragged_bwd(const float* dy, void* dx, const int64_t* flen, int32_t B, int32_t T, int32_t C,
+                                      int dtype, hipStream_t s) {
+  if (!dy || !dx || !flen || T <= 0 || C <= 0) return DFK_EINVAL;
+  if (B <= 0) return 0;
+  const long n = (long)B * T * C;
+  const dim3 grid((unsigned)dfk_cdiv(n, 256));
+  if (dtype == DFK_BF16)
+    hipLaunchKernelGGL(rowmean_ragged_bwd_kernel<bf16raw>, grid, dim3(256), 0, s, dy, (bf16raw*)dx, flen, (int)T, (int)C, n);
+  else
+    hipLaunchKernelGGL(rowmean_ragged_bwd_kernel<float>, grid, dim3(256), 0, s, dy, (float*)dx, flen, (int)T, (int)C, n);
   DFK_CHECK_LAUNCH();
   return 0;
 }

@@ -59,7 +59,8 @@ constexpr int kSpecSlices = 16;   // workgroups per clip in the SpecAugment forw
 template <typename T>
 __global__ __launch_bounds__(256) void spec_aug_fwd_kernel(const T* __restrict__ h, T* __restrict__ out,
                                                            uint8_t* __restrict__ mask, const T* __restrict__ embed,
-                                                           int Tn, int C, float mask_prob, int mlen, int min_masks,
+                                                           const int64_t* __restrict__ flen, int Tn, int C,
+                                                           float mask_prob, int mlen, int min_masks,
                                                            const dfk_drop d, int vec) {
   extern __shared__ int sm[];
   int* cand = sm;              // [Tn] candidate span starts (partial Fisher-Yates)
@@ -79,8 +80,11 @@ __global__ __launch_bounds__(256) void spec_aug_fwd_kernel(const T* __restrict__
       if (len - (mlen - 1) < n) n = max(len - (mlen - 1), 0);
       return n;
     };
-    const int n = num_spans(Tn);
-    const int R = Tn - (mlen - 1);   // candidate starts [0, R)
+    // ragged (flen): the clip's own frame count sets the span count and the range of the starts, so no frame
+    // at or past it is masked (HF with an attention mask, less its dummy index)
+    const int Tb = flen ? (int)min(max(flen[b], (int64_t)1), (int64_t)Tn) : Tn;
+    const int n = num_spans(Tb);
+    const int R = Tb - (mlen - 1);   // candidate starts [0, R)
     for (int i = 0; i < n; ++i) {    // n distinct starts, uniformly without replacement
       const uint32_t hsh = drop_hash(dc, b, i);
       const int j = i + (int)(hsh % (uint32_t)(R - i));
@@ -201,9 +205,10 @@ extern "C" int dfk_layer_select(const void* y, const void* x, const float* keep,
   return 0;
 }
 
-extern "C" int dfk_spec_augment_fwd(const void* h, void* out, uint8_t* mask, const void* embed, int32_t B, int32_t T,
-                                    int32_t C, float mask_prob, int32_t mask_length, int32_t min_masks,
-                                    const dfk_drop* d, int dtype, hipStream_t s) {
+extern "C" int dfk_spec_augment_ragged_fwd(const void* h, void* out, uint8_t* mask, const void* embed,
+                                           const int64_t* flen, int32_t B, int32_t T, int32_t C, float mask_prob,
+                                           int32_t mask_length, int32_t min_masks, const dfk_drop* d, int dtype,
+                                           hipStream_t s) {
   if (!h || !out || !mask || !embed || !d || !d->rng || mask_length <= 0 || C <= 0 || T > 16384) return DFK_EINVAL;
   if (B <= 0 || T <= 0) return 0;
   const size_t lds = 8 * (size_t)T;
@@ -211,12 +216,19 @@ extern "C" int dfk_spec_augment_fwd(const void* h, void* out, uint8_t* mask, con
   const int vec = C % (dtype == DFK_BF16 ? 8 : 4) == 0 && al(h) && al(out) && al(embed);
   if (dtype == DFK_BF16)
     hipLaunchKernelGGL(spec_aug_fwd_kernel<bf16raw>, dim3(B, kSpecSlices), dim3(256), lds, s, (const bf16raw*)h, (bf16raw*)out, mask,
-                       (const bf16raw*)embed, (int)T, (int)C, mask_prob, (int)mask_length, (int)min_masks, *d, vec);
+                       (const bf16raw*)embed, flen, (int)T, (int)C, mask_prob, (int)mask_length, (int)min_masks, *d, vec);
   else
     hipLaunchKernelGGL(spec_aug_fwd_kernel<float>, dim3(B, kSpecSlices), dim3(256), lds, s, (const float*)h, (float*)out, mask,
-                       (const float*)embed, (int)T, (int)C, mask_prob, (int)mask_length, (int)min_masks, *d, vec);
+                       (const float*)embed, flen, (int)T, (int)C, mask_prob, (int)mask_length, (int)min_masks, *d, vec);
   DFK_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int dfk_spec_augment_fwd(const void* h, void* out, uint8_t* mask, const void* embed, int32_t B, int32_t T,
+                                    int32_t C, float mask_prob, int32_t mask_length, int32_t min_masks,
+                                    const dfk_drop* d, int dtype, hipStream_t s) {
+  return dfk_spec_augment_ragged_fwd(h, out, mask, embed, nullptr, B, T, C, mask_prob, mask_length, min_masks, d, dtype,
+                                     s);
 }
 
 extern "C" int dfk_spec_augment_bwd(const void* dy, void* dx, const uint8_t* mask, float* dembed, int32_t B, int32_t T,

@@ -141,6 +141,15 @@ __device__ __forceinline__ T tok_ld1(const void* base, const void* pad, int row,
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) short4v lds_short4;
 
+// Per-clip key lengths (dfk_wattn_args.klen; the KL instantiations): one window per clip that covers it exactly, so
+// token i of clip b is row b N + i.  Tokens >= kn are staged as zero (their rows never reach arithmetic), score -inf
+// as keys, and are written as zero rows of out / dq / dk / dv.
+template <bool KL>
+__device__ __forceinline__ int key_len(const dfk_wattn_args& a, const Geo& g, int b) {
+  if constexpr (KL) return __builtin_amdgcn_readfirstlane(min(max(a.klen[b], 1), g.N));
+  return g.N;
+}
+
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kBwdWaves = 8;
 constexpr int kSdStride = 40;  // bf16 row stride of the per-wave dS^T scratch [32 keys][32 queries]
@@ -178,7 +187,7 @@ __device__ __forceinline__ float dot8_bf16(uint4 x, uint4 y) {
 }
 
 // ---------------------------------------------------------------- forward
-template <typename T, int HD>
+template <typename T, int HD, bool KL = false>
 __global__ __launch_bounds__(256) void wattn_fwd_kernel(const dfk_wattn_args a, const Geo g, int qsplit) {
   constexpr bool BF = sizeof(T) == 2;
   constexpr int VEC = 16 / sizeof(T);
@@ -197,8 +206,13 @@ __global__ __launch_bounds__(256) void wattn_fwd_kernel(const dfk_wattn_args a, 
   unit /= a.heads;
   const int win = unit % g.nW, b = unit / g.nW;
   const float* mrow = a.mask ? a.mask + (((long)b * g.nW + win) % a.mask_nw) * g.N * g.N : nullptr;
+  const int kn = key_len<KL>(a, g, b);
 
-  for (int i = tid; i < g.Np; i += 256) tok[i] = token_info(a, g, b, win, i);
+  for (int i = tid; i < g.Np; i += 256) {
+    TokInfo t = token_info(a, g, b, win, i);
+    if (KL && i >= kn) t.row = -2;
+    tok[i] = t;
+  }
   if (a.rpb)
     for (int l = tid; l < g.L; l += 256) rpb[l] = a.rpb[(long)l * a.heads + head];
   __syncthreads();
@@ -222,9 +236,17 @@ __global__ __launch_bounds__(256) void wattn_fwd_kernel(const dfk_wattn_args a, 
 
   const int grp = lane >> 4, ql = lane & 15;
   const int nqt = (g.N + 15) / 16;
-  const int nkb = g.Np / 32;
+  const int nkb = KL ? (kn + 31) / 32 : g.Np / 32;   // key blocks wholly past kn are skipped
   for (int qt = dfk_bid_y() * 4 + wave; qt < nqt; qt += 4 * qsplit) {
     const int q = qt * 16 + ql;
+    if (KL && qt * 16 >= kn) {   // a query tile wholly past kn: zero rows, no arithmetic
+      if (q < g.N) {
+        T* op = reinterpret_cast<T*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff;
+        for (int e = grp * (HD / 4); e < (grp + 1) * (HD / 4); ++e) op[e] = (T)0;
+        if (a.lse && grp == 0) a.lse[((long)dfk_bid_x()) * g.Np + q] = 0.f;
+      }
+      continue;
+    }
     const TokInfo tq = q < g.N ? tok[q] : TokInfo{-2, 0, -1};
     // Q fragment (B operand: lane holds Q[q][e-slots])
     const T* qp = tok_ptr<T>(a.q, a.pad_q, tq.row, a.ld_qkv, hoff);
@@ -363,8 +385,11 @@ __global__ __launch_bounds__(256) void wattn_fwd_kernel(const dfk_wattn_args a, 
               make_float4(o[et][0] * inv, o[et][1] * inv, o[et][2] * inv, o[et][3] * inv);
         }
       }
+    } else if (KL && q < g.N) {   // a row past kn in the tile that holds kn
+      T* op = reinterpret_cast<T*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff;
+      for (int e = grp * (HD / 4); e < (grp + 1) * (HD / 4); ++e) op[e] = (T)0;
     }
-    if (a.lse && grp == 0 && q < g.N) a.lse[((long)dfk_bid_x()) * g.Np + q] = m + __logf(l);
+    if (a.lse && grp == 0 && q < g.N) a.lse[((long)dfk_bid_x()) * g.Np + q] = (KL && q >= kn) ? 0.f : m + __logf(l);
   }
 }
 
@@ -827,7 +852,7 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
 //   O^T += V^T P^T, l = ones^T P^T (both on the MFMA; P^T is the accumulator tile converted in place)
 // with a lazy rescale (m moves only when a block's max exceeds it by kRescale, or on the first block).
 // Lane l holds query 32 qb + (l & 31) and keys (j & 3) + 8 (j >> 2) + 4 (l >> 5) of every tile.
-template <int HD, bool DROP>
+template <int HD, bool DROP, bool KL = false>
 __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_kernel(const dfk_wattn_args a, const Geo g, int qsplit,
                                                          const bf16raw* __restrict__ /* the table kernels' launch signature */) {
   constexpr int NKK = HD / 16, NOT = HD / 32, CH = HD / 8;
@@ -840,12 +865,14 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
   const int head = wu.head, win = wu.win, b = wu.b;
   const long unit = wu.lse_unit;
   const int hoff = head * HD;
+  const int kn = key_len<KL>(a, g, b);
+  const int nkb = KL ? (kn + 31) / 32 : g.Np / 32, nqb = g.Np / 32;   // key blocks wholly past kn: not staged, not run
   // K / V gather, KV_B chunks per thread in flight: every load of a batch is issued (clamped, branch-free
   // addresses) before the one wait that precedes its LDS writes — a load / wait / write chain per chunk
   // costs one HBM round trip each (7 K + 7 V per thread at Np 416)
   {
     constexpr int KV_B = 4;
-    const int tot = g.Np * CH;
+    const int tot = nkb * 32 * CH;
     for (int base = tid; base < tot; base += KV_B * dfk_bdim()) {
       uint4 kv[KV_B], vv[KV_B];
       int off[KV_B];
@@ -853,7 +880,7 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
       for (int u = 0; u < KV_B; ++u) {
         const int idx = min(base + u * (int)dfk_bdim(), tot - 1);
         const int i = idx / CH, c = (idx % CH) * 8;
-        const int row = token_info_row(a, g, b, win, i);
+        const int row = KL && i >= kn ? -2 : token_info_row(a, g, b, win, i);
         off[u] = swz<HD>(i, c);
         kv[u] = tok_ld16<bf16raw>(a.k, a.pad_k, row, a.ld_qkv, hoff + c);
         vv[u] = tok_ld16<bf16raw>(a.v, a.pad_v, row, a.ld_qkv, hoff + c);
@@ -867,7 +894,6 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
       }
     }
   }
-  const int nkb = g.Np / 32, nqb = g.Np / 32;
   const bf16x8 sel = rowsum_sel(lane);
   const float qs = a.scale * kLog2e;
   const DropCtx dc = drop_ctx(a.drop);
@@ -878,7 +904,7 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
   bf16x8 qfn[NKK];
   auto load_q = [&](int qb) {   // Q'^T B operands of query 32 qb + r: elements 8 hh + j of each 16-wide k-step
     const int q = qb * 32 + r;
-    qrown = q < g.N ? token_info_row(a, g, b, win, q) : -2;
+    qrown = q < kn ? token_info_row(a, g, b, win, q) : -2;
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk)
       qfn[kk] = __builtin_bit_cast(bf16x8, tok_ld16<bf16raw>(a.q, a.pad_q, qrown, a.ld_qkv, hoff + kk * 16 + hh * 8));
@@ -902,6 +928,16 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
   for (int j = 0; j < 8; ++j) onesA[j] = (__bf16)(hh == 0 && j == 0 ? 1.f : 0.f);
   load_q(min(wu.qpart * nw + wave, nqb - 1));
   for (int qb = wu.qpart * nw + wave; qb < nqb; qb += qstep) {
+    if (KL && qb * 32 >= kn) {   // a query block wholly past kn: zero rows, no arithmetic (so are all the later ones)
+      const int q = qb * 32 + r;
+      if (q < g.N) {
+        bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff + hh * (HD / 2);
+#pragma unroll
+        for (int c = 0; c < HD / 16; ++c) *reinterpret_cast<uint4*>(op + 8 * c) = make_uint4(0, 0, 0, 0);
+        if (a.lse && hh == 0) a.lse[unit * g.Np + q] = 0.f;
+      }
+      continue;
+    }
     const int qrow = qrown;
     bf16x8 qf[NKK];
 #pragma unroll
@@ -927,10 +963,10 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
       f32x16 d = mfma32(onesA, mB, f32x16{});
 #pragma unroll
       for (int kk = 0; kk < NKK; ++kk) d = mfma32(*reinterpret_cast<const bf16x8*>(kbase + koff[kk]), qf[kk], d);
-      if (kb == nkb - 1) {   // keys beyond N (no table: the only padded key block)
+      if (kb == nkb - 1) {   // keys beyond N, or beyond kn (no table: the only padded key block)
 #pragma unroll
         for (int j = 0; j < 16; ++j)
-          if (kb * 32 + (j & 3) + 8 * (j >> 2) + 4 * hh >= g.N) d[j] = -INFINITY;
+          if (kb * 32 + (j & 3) + 8 * (j >> 2) + 4 * hh >= kn) d[j] = -INFINITY;
       }
       // lazy rescale: the block max relative to m (lanes l and l^32 hold the same query)
       float x0 = max3f(d[0], d[1], d[2]), x1 = max3f(d[3], d[4], d[5]), x2 = max3f(d[6], d[7], d[8]);
@@ -1002,7 +1038,13 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
         }
     }
     const int q = qb * 32 + r;
-    if (a.lse && hh == 0 && q < g.N) a.lse[unit * g.Np + q] = (m + __log2f(l)) * 0.6931471805599453f;
+    if (KL && q >= kn && q < g.N) {   // a row past kn in the block that holds kn
+      bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff + hh * (HD / 2);
+#pragma unroll
+      for (int c = 0; c < HD / 16; ++c) *reinterpret_cast<uint4*>(op + 8 * c) = make_uint4(0, 0, 0, 0);
+    }
+    if (a.lse && hh == 0 && q < g.N)
+      a.lse[unit * g.Np + q] = (KL && q >= kn) ? 0.f : (m + __log2f(l)) * 0.6931471805599453f;
   }
 }
 
@@ -1924,6 +1966,14 @@ bool args_ok(const dfk_wattn_args& a) {
   return true;
 }
 
+// klen (per-clip key lengths): one window per clip that covers it exactly, and no bias, shift, mask or pad vectors;
+// bf16 runs the no-bias v3 kernels only
+bool klen_ok(const dfk_wattn_args& a, const Geo& g) {
+  if (g.nW != 1 || a.wd != a.D || a.wh != a.H || a.ww != a.W) return false;
+  if (a.rpb || a.mask || g.use_mask || a.pad_q || a.pad_k || a.pad_v) return false;
+  return a.dtype != DFK_BF16 || a.scale > 0.f;
+}
+
 size_t fwd_lds(const dfk_wattn_args& a, const Geo& g) {
   const size_t es = a.dtype == DFK_BF16 ? 2 : 4;
   size_t v = a.dtype == DFK_BF16 ? (size_t)a.hd * (g.Np + 8) * es : (size_t)g.Np * a.hd * es;
@@ -1995,6 +2045,7 @@ bool use_v6(const dfk_wattn_args& a, const Geo& g) {
 
 extern "C" int dfk_wattn_table(const dfk_wattn_args* ap, hipStream_t s) {
   if (!ap || !args_ok(*ap) || !ap->tab || ap->dtype != DFK_BF16 || ap->mask || !(ap->scale > 0.f)) return DFK_EINVAL;
+  if (ap->klen) return DFK_EINVAL;
   const dfk_wattn_args& a = *ap;
   const Geo g = make_geo(a);
   const TabGeo tg = tab_geo(a, g);
@@ -2027,6 +2078,7 @@ extern "C" int dfk_wattn_fwd(const dfk_wattn_args* ap, hipStream_t s) {
   if (!ap || !args_ok(*ap)) return DFK_EINVAL;
   const dfk_wattn_args& a = *ap;
   const Geo g = make_geo(a);
+  if (a.klen && !klen_ok(a, g)) return DFK_EINVAL;
   if (a.drop.mode && !(a.dtype == DFK_BF16 && !a.mask && a.scale > 0.f)) return DFK_EINVAL;  // bf16 v3 path only
   const long units = (long)a.B * g.nW * a.heads;
   if (table_path(a, g)) {
@@ -2052,7 +2104,12 @@ extern "C" int dfk_wattn_fwd(const dfk_wattn_args* ap, hipStream_t s) {
     const dim3 grid((unsigned)(units * qsplit)), block(64 * nw);
     // bias tables: v6 / v5 / v4 (bias through the QK^T C input, VALU row sums); no bias: v3
     const bool drop = a.drop.mode != 0;
-    if (a.hd == 32) {
+    if (a.klen) {   // per-clip key lengths: v3's KL instantiations (klen_ok: no bias)
+      if (a.hd == 32 && drop) launch_lds<wattn_fwd3_kernel<32, true, true>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (a.hd == 32) launch_lds<wattn_fwd3_kernel<32, false, true>>(grid, block, lds, s, a, g, qsplit, t3);
+      else if (drop) launch_lds<wattn_fwd3_kernel<64, true, true>>(grid, block, lds, s, a, g, qsplit, t3);
+      else launch_lds<wattn_fwd3_kernel<64, false, true>>(grid, block, lds, s, a, g, qsplit, t3);
+    } else if (a.hd == 32) {
       if (!tab && drop) launch_lds<wattn_fwd3_kernel<32, true>>(grid, block, lds, s, a, g, qsplit, t3);
       else if (!tab) launch_lds<wattn_fwd3_kernel<32, false>>(grid, block, lds, s, a, g, qsplit, t3);
       else if (drop) launch_lds<wattn_fwd4_kernel<32, true, 1>>(grid, block, lds, s, a, g, qsplit, t3);
@@ -2099,7 +2156,9 @@ extern "C" int dfk_wattn_fwd(const dfk_wattn_args* ap, hipStream_t s) {
   const int nqt = dfk_cdiv(g.N, 16);
   const int qsplit = (int)std::max<long>(1, std::min<long>(dfk_cdiv(nqt, 4), dfk_cdiv(1024, units)));
   const dim3 grid((unsigned)units, qsplit);
-  if (a.hd == 32) launch_lds<wattn_fwd_kernel<float, 32>>(grid, dim3(256), lds, s, a, g, qsplit);
+  if (a.klen && a.hd == 32) launch_lds<wattn_fwd_kernel<float, 32, true>>(grid, dim3(256), lds, s, a, g, qsplit);
+  else if (a.klen) launch_lds<wattn_fwd_kernel<float, 64, true>>(grid, dim3(256), lds, s, a, g, qsplit);
+  else if (a.hd == 32) launch_lds<wattn_fwd_kernel<float, 32>>(grid, dim3(256), lds, s, a, g, qsplit);
   else launch_lds<wattn_fwd_kernel<float, 64>>(grid, dim3(256), lds, s, a, g, qsplit);
   DFK_CHECK_LAUNCH();
   return 0;
@@ -2148,7 +2207,26 @@ __global__ __launch_bounds__(1024) void drpb_reduce_kernel(const float* __restri
   }
 }
 
-template <typename T, int HD>
+// This wave's partial dQ tile of query block qb into the LDS accumulator, the four waves in turn: a fixed order of
+// the adds (float atomics from the four waves made dQ differ in its last bit from run to run).  Every wave of the
+// workgroup calls it once per step, or runs the four barriers.
+template <int HD>
+__device__ __forceinline__ void dq_add_in_turn(float* dQacc, const f32x4 (&p)[2][HD / 16], int qb, int wave, int grp,
+                                               int ql) {
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int qh = 0; qh < 2; ++qh)
+#pragma unroll
+        for (int et = 0; et < HD / 16; ++et)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dQacc[(qb * 32 + qh * 16 + grp * 4 + r) * HD + et * 16 + ql] += p[qh][et][r];
+    }
+    __syncthreads();
+  }
+}
+
+template <typename T, int HD, bool KL = false>
 __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args ba, const Geo g, int q0, int Qn,
                                                         int accum_kv) {
   // queries [q0, q0+Qn) of every window are handled by this launch (Qn % 32 == 0);
@@ -2177,8 +2255,13 @@ __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args
   const float* mrow = a.mask ? a.mask + (((long)b * g.nW + win) % a.mask_nw) * g.N * g.N : nullptr;
   const int hoff = head * HD;
   constexpr int VEC = 16 / sizeof(T);
+  const int kn = key_len<KL>(a, g, b);
 
-  for (int i = tid; i < g.Np; i += 256) tok[i] = token_info(a, g, b, win, i);
+  for (int i = tid; i < g.Np; i += 256) {
+    TokInfo t = token_info(a, g, b, win, i);
+    if (KL && i >= kn) t.row = -2;   // staged as zero, P = 0
+    tok[i] = t;
+  }
   for (int l = tid; l < g.L; l += 256) {
     rpb[l] = a.rpb ? a.rpb[(long)l * a.heads + head] : 0.f;
     drpb[l] = 0.f;
@@ -2203,13 +2286,32 @@ __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args
       for (int e = 0; e < HD; ++e) d += ldf<T>(op + e) * ldf<T>(dop + e);
     }
     delta[li] = d;
-    lse[li] = (i < g.N) ? a.lse[(long)dfk_bid_x() * g.Np + i] : 0.f;
+    lse[li] = (i < kn) ? a.lse[(long)dfk_bid_x() * g.Np + i] : 0.f;
   }
   __syncthreads();
 
   T* Sw = Sd + wave * 32 * 32;
-  const int nkb = g.Np / 32, nqb = Qn / 32;
-  for (int kb = wave; kb < nkb; kb += 4) {
+  // KL: key blocks and query blocks wholly past kn are skipped
+  const int nkb = KL ? (kn + 31) / 32 : g.Np / 32, nqb = KL ? min(Qn / 32, max(0, (kn - q0 + 31) / 32)) : Qn / 32;
+  if constexpr (KL) {   // dK / dV rows of the skipped key blocks
+    if (!accum_kv)
+      for (int idx = tid; idx < (g.Np - nkb * 32) * (HD / 4); idx += 256) {
+        const int k = nkb * 32 + idx / (HD / 4), e = hoff + (idx % (HD / 4)) * 4;
+        if (k < g.N) {
+          const long o = ((long)b * g.N + k) * ba.ld_dqkv + e;
+          for (int j = 0; j < 4; ++j) {
+            stf<T>(reinterpret_cast<T*>(ba.dk) + o + j, 0.f);
+            stf<T>(reinterpret_cast<T*>(ba.dv) + o + j, 0.f);
+          }
+        }
+      }
+  }
+  for (int kb0 = 0; kb0 < nkb; kb0 += 4) {
+    const int kb = kb0 + wave;
+    if (kb >= nkb) {   // no key block this pass: keep dq_add_in_turn's barriers
+      for (int i = 0; i < 4 * nqb; ++i) __syncthreads();
+      continue;
+    }
     // own keys: B fragments of K^T and V^T (key on lane) and K in natural-k B layout for dQ
     f32x4 dK[2][HD / 16], dV[2][HD / 16];
 #pragma unroll
@@ -2298,17 +2400,15 @@ __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args
           }
         }
         // dQ[q][e] += scale * sum_k dS[q][k] K[k][e]  (natural k order through the wave's scratch)
+        f32x4 dqp[2][HD / 16];
 #pragma unroll
         for (int qh = 0; qh < 2; ++qh) {
           const bf16x8 sa = *reinterpret_cast<const bf16x8*>(Sw + (qh * 16 + ql) * 32 + grp * 8);
 #pragma unroll
-          for (int et = 0; et < HD / 16; ++et) {
-            f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sa, kN[et], f32x4{0, 0, 0, 0}, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              atomicAdd(dQacc + (qb * 32 + qh * 16 + grp * 4 + r) * HD + et * 16 + ql, acc[r] * a.scale);
-          }
+          for (int et = 0; et < HD / 16; ++et)
+            dqp[qh][et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sa, kN[et], f32x4{0, 0, 0, 0}, 0, 0, 0) * a.scale;
         }
+        dq_add_in_turn<HD>(dQacc, dqp, qb, wave, grp, ql);
       }
     } else {
       float kB[2][HD / 4], vB[2][HD / 4], kN[HD / 16][8];
@@ -2366,6 +2466,7 @@ __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args
             }
           }
         }
+        f32x4 dqp[2][HD / 16];
 #pragma unroll
         for (int qh = 0; qh < 2; ++qh)
 #pragma unroll
@@ -2374,10 +2475,9 @@ __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks)
               acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Sw[(qh * 16 + ql) * 32 + ks * 4 + grp], kN[et][ks], acc, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              atomicAdd(dQacc + (qb * 32 + qh * 16 + grp * 4 + r) * HD + et * 16 + ql, acc[r] * a.scale);
+            dqp[qh][et] = acc * a.scale;
           }
+        dq_add_in_turn<HD>(dQacc, dqp, qb, wave, grp, ql);
       }
     }
     // write dK (scaled) and dV for the 32 owned keys: C layout col = e (lane), row = key 4g+r
@@ -2399,6 +2499,9 @@ __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args
           } else if (t.row == -1) {
             if (ba.dpad_k) atomicAdd(ba.dpad_k + e, vk);
             if (ba.dpad_v) atomicAdd(ba.dpad_v + e, vv);
+          } else if (KL && k < g.N) {   // a key past kn in the block that holds kn
+            stf<T>(reinterpret_cast<T*>(ba.dk) + ((long)b * g.N + k) * ba.ld_dqkv + e, 0.f);
+            stf<T>(reinterpret_cast<T*>(ba.dv) + ((long)b * g.N + k) * ba.ld_dqkv + e, 0.f);
           }
         }
       }
@@ -2411,6 +2514,7 @@ __global__ __launch_bounds__(256) void wattn_bwd_kernel(const dfk_wattn_bwd_args
     const TokInfo t = tok[i];
     if (t.row >= 0) stf<T>(reinterpret_cast<T*>(ba.dq) + (long)t.row * ba.ld_dqkv + hoff + e, dQacc[idx]);
     else if (t.row == -1 && ba.dpad_q) atomicAdd(ba.dpad_q + hoff + e, dQacc[idx]);
+    else if (KL && t.row == -2) stf<T>(reinterpret_cast<T*>(ba.dq) + ((long)b * g.N + i) * ba.ld_dqkv + hoff + e, 0.f);
   }
   if (a.rpb && ba.drpb) flush_drpb(ba, g, drpb, head, accum_kv, tid, 256);
 }
@@ -2778,7 +2882,7 @@ __device__ __forceinline__ float halving_sum16_fn(F f, int lane) {
   return v[0] + __shfl_xor(v[0], 1, 64);
 }
 
-template <int HD, bool TAB, bool DROP, bool COS = false>
+template <int HD, bool TAB, bool DROP, bool COS = false, bool KL = false>
 __global__ __launch_bounds__(COS ? 256 : 512) void wattn_bwd3_kernel(const dfk_wattn_bwd_args ba, const Geo g, int q0, int Qn,
                                                          int accum_kv, bf16raw* __restrict__ dsg,
                                                          const bf16raw* __restrict__ tabb, int G) {
@@ -2801,6 +2905,7 @@ __global__ __launch_bounds__(COS ? 256 : 512) void wattn_bwd3_kernel(const dfk_w
   float* rowB = reinterpret_cast<float*>(p); p += COS ? 4 * Qn : 0;
   float* red = reinterpret_cast<float*>(p); p += COS ? 4 * 16 : 0;
   static_assert(!(COS && (DROP || !TAB)), "COS: bias-table path without dropout");
+  static_assert(!(KL && (TAB || COS)), "KL: the no-bias kernels");
 
   const int tid = dfk_tid(), lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, hh = lane >> 5, g16 = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
@@ -2819,10 +2924,12 @@ __global__ __launch_bounds__(COS ? 256 : 512) void wattn_bwd3_kernel(const dfk_w
   const __amdgpu_buffer_rsrc_t trs =
       __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(tpu), (short)0, TAB ? 0x7fffffff : 0, 0x00020000);
   const float qs = a.scale * kLog2e;
+  const int kn = key_len<KL>(a, g, b);
+  const int nkbe = KL ? (kn + 31) / 32 : nkb;   // key blocks that hold a key below kn
 
-  for (int i = tid; i < Np; i += dfk_bdim()) trow[i] = token_info_row(a, g, b, win, i);
+  for (int i = tid; i < Np; i += dfk_bdim()) trow[i] = KL && i >= kn ? -2 : token_info_row(a, g, b, win, i);
   for (int i = tid; i < Qn; i += dfk_bdim())
-    nl2[i] = q0 + i < g.N ? -a.lse[unit * Np + q0 + i] * kLog2e : -INFINITY;
+    nl2[i] = q0 + i < kn ? -a.lse[unit * Np + q0 + i] * kLog2e : -INFINITY;
   for (int i = tid * 4; i < Qn * HD; i += dfk_bdim() * 4) *reinterpret_cast<f32x4*>(dQa + i) = f32x4{0, 0, 0, 0};
   if constexpr (COS)
     for (int i = tid; i < Qn; i += dfk_bdim()) rowD[i] = rowB[i] = 0.f;
@@ -2879,13 +2986,24 @@ __global__ __launch_bounds__(COS ? 256 : 512) void wattn_bwd3_kernel(const dfk_w
   }
   for (int pass = 0; pass * nw < nkb; ++pass) {
     const int kb = pass * nw + wave;
-    if (kb >= nkb) {   // no key block this pass: keep the step barriers
+    if (kb >= nkbe) {   // no key block this pass, or one wholly past kn: keep the step barriers
+      if constexpr (KL) {   // its dK / dV rows are zero (a later query chunk finds them so)
+        const int k = kb * 32 + r;
+        if (kb < nkb && k < g.N && !accum_kv) {
+          const long o = ((long)b * g.N + k) * ba.ld_dqkv + hoff + hh * (HD / 2);
+#pragma unroll
+          for (int c = 0; c < HD / 16; ++c) {
+            *reinterpret_cast<uint4*>(reinterpret_cast<bf16raw*>(ba.dk) + o + 8 * c) = make_uint4(0, 0, 0, 0);
+            *reinterpret_cast<uint4*>(reinterpret_cast<bf16raw*>(ba.dv) + o + 8 * c) = make_uint4(0, 0, 0, 0);
+          }
+        }
+      }
       for (int i = 0; i < nqb; ++i) __syncthreads();
       continue;
     }
     // K^T / V^T B operands (key on the lane) and K as the B operand of dQ = dS K (e on the lane)
     const int krow = trow[kb * 32 + r];
-    const float kneg = kb * 32 + r < g.N ? 0.f : -INFINITY;   // keys beyond N (the bias tiles also hold -1e4 there)
+    const float kneg = kb * 32 + r < kn ? 0.f : -INFINITY;   // keys beyond N (the bias tiles also hold -1e4 there)
     bf16x8 kB[NKK], vB[NKK], kN[2][NOT];
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk) {
@@ -2938,6 +3056,10 @@ __global__ __launch_bounds__(COS ? 256 : 512) void wattn_bwd3_kernel(const dfk_w
     load_bias(qb);
     for (int i = 0; i < nqb; ++i, qb = qb + 1 == nqb ? 0 : qb + 1) {
       const int qr0 = qb * 32;   // local row of the block in the chunk
+      if (KL && q0 + qr0 >= kn) {   // a query block wholly past kn: no work, the step barrier kept
+        __syncthreads();
+        continue;
+      }
       bf16raw* const gp = dsu ? dsu + (long)(kb * 32 + (lane >> 1)) * Np + q0 + qr0 + (lane & 1) * 16 : nullptr;
       // row constants as the C inputs: queries q0 + 8 v + 4 hh + (0..3) in registers 4v .. 4v+3
       f32x16 s, dp;
@@ -3109,6 +3231,10 @@ __global__ __launch_bounds__(COS ? 256 : 512) void wattn_bwd3_kernel(const dfk_w
             if (ba.dpad_k) atomicAdd(ba.dpad_k + e + t, dKt[ot][4 * v + t] * kscale);
             if (ba.dpad_v) atomicAdd(ba.dpad_v + e + t, dVt[ot][4 * v + t]);
           }
+        } else if (KL && kb * 32 + r < g.N) {   // a key past kn in the block that holds kn
+          const long o = ((long)b * g.N + kb * 32 + r) * ba.ld_dqkv + e;
+          *reinterpret_cast<uint2*>(reinterpret_cast<bf16raw*>(ba.dk) + o) = make_uint2(0, 0);
+          *reinterpret_cast<uint2*>(reinterpret_cast<bf16raw*>(ba.dv) + o) = make_uint2(0, 0);
         }
       }
   }
@@ -3144,6 +3270,9 @@ __global__ __launch_bounds__(COS ? 256 : 512) void wattn_bwd3_kernel(const dfk_w
     } else if (row == -1 && ba.dpad_q) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) atomicAdd(ba.dpad_q + hoff + c + j, vv[j]);
+    } else if (KL && q0 + i < g.N) {   // a query past kn
+      *reinterpret_cast<uint4*>(reinterpret_cast<bf16raw*>(ba.dq) + ((long)b * g.N + q0 + i) * ba.ld_dqkv + hoff + c) =
+          make_uint4(0, 0, 0, 0);
     }
   }
   __syncthreads();   // the next window of the group reuses trow / dQa / the statistics
@@ -3771,6 +3900,7 @@ extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
   const int vec = a.dtype == DFK_BF16 ? 8 : 4;
   if (bp->ld_dqkv % vec || bp->ld_dout % vec) return DFK_EINVAL;
   const Geo g = make_geo(a);
+  if (a.klen && !klen_ok(a, g)) return DFK_EINVAL;
   const long units = (long)a.B * g.nW * a.heads;
   if (table_path(a, g)) {
     // v3 (the forward's bias tiles, bwd layout)
@@ -3799,7 +3929,13 @@ extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
     const dim3 grid((unsigned)(slabw * a.heads));
     const dim3 block(64 * nw);
     const bool drop = a.drop.mode != 0;
-    if (v4) {   // the two-pass kernel (the v6 windows)
+    if (a.klen) {   // per-clip key lengths: the single-pass kernel's KL instantiations (klen_ok: no bias)
+      if (cos) return DFK_EINVAL;
+      if (a.hd == 32 && drop) launch_chunks<wattn_bwd3_kernel<32, false, true, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (a.hd == 32) launch_chunks<wattn_bwd3_kernel<32, false, false, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else if (drop) launch_chunks<wattn_bwd3_kernel<64, false, true, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+      else launch_chunks<wattn_bwd3_kernel<64, false, false, false, true>>(Qn, grid, block, lds, s, *bp, g, dsg, tb, G);
+    } else if (v4) {   // the two-pass kernel (the v6 windows)
       launch_lds<wattn_bwd4_kernel>(grid, dim3(64 * kB4Waves), bwd4_lds(g), s, *bp, g, dsg, tab3_fwd(a, g), tb, G,
                                     b4_sched(g.Np / 32));
     } else if (a.hd == 32) {
@@ -3856,7 +3992,9 @@ extern "C" int dfk_wattn_bwd(const dfk_wattn_bwd_args* bp, hipStream_t s) {
   if (lds > 160 * 1024) return DFK_EINVAL;
   if (units <= 0) return 0;
   const dim3 grid((unsigned)units), block(256);
-  if (a.hd == 32) launch_chunks<wattn_bwd_kernel<float, 32>>(Qn, grid, block, lds, s, *bp, g);
+  if (a.klen && a.hd == 32) launch_chunks<wattn_bwd_kernel<float, 32, true>>(Qn, grid, block, lds, s, *bp, g);
+  else if (a.klen) launch_chunks<wattn_bwd_kernel<float, 64, true>>(Qn, grid, block, lds, s, *bp, g);
+  else if (a.hd == 32) launch_chunks<wattn_bwd_kernel<float, 32>>(Qn, grid, block, lds, s, *bp, g);
   else launch_chunks<wattn_bwd_kernel<float, 64>>(Qn, grid, block, lds, s, *bp, g);
   reduce_drpb(*bp, g, units, s);
   DFK_CHECK_LAUNCH();

@@ -381,7 +381,7 @@ class WindowAttnFn(torch.autograd.Function):
     [3C] (the padded positions' q/k/v, or None), explicit mask or None."""
 
     @staticmethod
-    def forward(ctx, qkv, rpb, qkv_bias, mask, geo, drop=None, dscore=None):
+    def forward(ctx, qkv, rpb, qkv_bias, mask, geo, drop=None, dscore=None, klen=None):
         dims, window, full_window, shift, heads, hd, scale = geo
         C = heads * hd
         pads = None
@@ -390,8 +390,9 @@ class WindowAttnFn(torch.autograd.Function):
             pads = (bc[:C], bc[C:2 * C], bc[2 * C:])
         rpb_f = rpb.detach().float().contiguous() if rpb is not None else None
         out, lse, tab = K.wattn_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], qkv.stride(0), dims, window, full_window, shift,
-                                    heads, hd, scale, rpb=rpb_f, pads=pads, mask=mask, return_table=True, drop=drop)
-        ctx.tab = tab
+                                    heads, hd, scale, rpb=rpb_f, pads=pads, mask=mask, return_table=True, drop=drop,
+                                    klen=klen)
+        ctx.tab, ctx.klen = tab, klen
         # a batched CPB table (Fn.cpb_tables) hands its slice of the shared gradient buffer to its first consumer
         # only: a second consumer of the same table gets a fresh gradient, which autograd adds out of place
         ctx.gview = rpb.__dict__.pop("_dfk_gview", None) if rpb is not None else None
@@ -419,22 +420,26 @@ class WindowAttnFn(torch.autograd.Function):
         dpads = [dbias[i * C:(i + 1) * C] for i in range(3)] if ctx.has_bias else None
         K.wattn_bwd((qkv, qkv[:, C:], qkv[:, 2 * C:], out, lse, qkv.stride(0), dims, window, full_window, shift, heads,
                      hd, scale, rpb_f, ctx.pads), dout.contiguous(), dqkv, dqkv[:, C:], dqkv[:, 2 * C:], qkv.stride(0),
-                    drpb=drpb, dpads=dpads, mask=mask, tab=ctx.tab, drop=ctx.drop, dscore=ctx.dscore)
+                    drpb=drpb, dpads=dpads, mask=mask, tab=ctx.tab, drop=ctx.drop, dscore=ctx.dscore, klen=ctx.klen)
         ctx.tab = None
         if ctx.has_rpb:
             drpb = grad_done(rpb, drpb)
         if ctx.has_bias:
             dbias = grad_done(qkv_bias, dbias)
-        return dqkv, drpb, dbias, None, None, None, None
+        return dqkv, drpb, dbias, None, None, None, None, None
 
 
-def window_attention(qkv, rpb, qkv_bias, geo, mask=None, drop=None, dscore=None):
-    """drop: attention-probability dropout (bf16 table path only).  dscore: [heads] fp32 buffer the backward adds
+def window_attention(qkv, rpb, qkv_bias, geo, mask=None, drop=None, dscore=None, klen=None):
+    """klen: int32 [B] device tensor of valid tokens per clip (a key-padding mask as lengths; one whole-clip window
+    without rpb, bias, shift or mask): keys past it are masked, rows past it are never read and come out as zero, as
+    do their dq / dk / dv.  drop: attention-probability dropout (bf16 table path only).  dscore: [heads] fp32 buffer the backward adds
     sum dS * score into (SwinV2's logit_scale gradient, consumed and re-zeroed by CosineQKFn's backward; bf16
     table path without dropout only; the models pass none: CosineQKFn derives that gradient from q-hat . dq')."""
     if drop is not None and qkv.dtype != torch.bfloat16:
         raise NotImplementedError("attention dropout runs in the bf16 table kernels only (fp32 parity mode: p = 0)")
-    return WindowAttnFn.apply(qkv, rpb, qkv_bias, mask, geo, drop, dscore)
+    if klen is None:
+        return WindowAttnFn.apply(qkv, rpb, qkv_bias, mask, geo, drop, dscore)
+    return WindowAttnFn.apply(qkv, rpb, qkv_bias, mask, geo, drop, dscore, klen)
 
 
 class DropoutFn(torch.autograd.Function):
@@ -470,9 +475,9 @@ class SpecAugmentFn(torch.autograd.Function):
     """HF Wav2Vec2Model._mask_hidden_states time masking (:1272-1317): masked frames <- masked_spec_embed."""
 
     @staticmethod
-    def forward(ctx, h, embed, mask_prob, mask_length, min_masks, drop):
+    def forward(ctx, h, embed, mask_prob, mask_length, min_masks, drop, flen=None):
         e = compute_weight(embed, h.dtype).contiguous()
-        out, mask = K.spec_augment_fwd(h.contiguous(), e, mask_prob, mask_length, min_masks, drop)
+        out, mask = K.spec_augment_fwd(h.contiguous(), e, mask_prob, mask_length, min_masks, drop, flen)
         grad_use(ctx, 1, embed)
         ctx.save_for_backward(mask, embed)
         return out
@@ -482,7 +487,37 @@ class SpecAugmentFn(torch.autograd.Function):
         mask, embed = ctx.saved_tensors
         de = grad_sink(embed)
         dx = K.spec_augment_bwd(dy.contiguous(), mask, de)
-        return dx, grad_done(embed, de), None, None, None, None
+        return dx, grad_done(embed, de), None, None, None, None, None
+
+
+class RowMaskFn(torch.autograd.Function):
+    """Padded batches: x [B, T, C] with the frames t >= flen[b] (device int64 [B]) set to zero by a select, and the
+    same op on the gradient (HF's hidden_states[~attention_mask] = 0, :761-764)."""
+
+    @staticmethod
+    def forward(ctx, x, flen):
+        ctx.save_for_backward(flen)
+        return K.row_mask(x, flen)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (flen,) = ctx.saved_tensors
+        return K.row_mask(dy, flen), None
+
+
+class RowMeanRaggedFn(torch.autograd.Function):
+    """x [B, T, C] -> fp32 [B, C] mean over each clip's own frames t < flen[b]."""
+
+    @staticmethod
+    def forward(ctx, x, flen):
+        ctx.save_for_backward(flen)
+        ctx.T, ctx.dtype = x.shape[1], x.dtype
+        return K.rowmean_ragged(x, flen)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (flen,) = ctx.saved_tensors
+        return K.rowmean_ragged_bwd(dy.float(), flen, ctx.T, ctx.dtype), None
 
 
 class PatchMergeFn(torch.autograd.Function):

@@ -362,8 +362,12 @@ def layernorm_bwd(dy, x, w, mean, rstd, dw, db, dx=None, accumulate=False, slab_
 
 
 def wattn_args(q, k, v, out, ld_qkv, dims, window, full_window, shift, heads, hd, scale, rpb=None, pads=None,
-               lse=None, mask=None, drop=None):
+               lse=None, mask=None, drop=None, klen=None):
     a = L.WattnArgs()
+    if klen is not None:
+        if klen.dtype != torch.int32 or klen.shape != (int(dims[0]),) or not klen.is_cuda or not klen.is_contiguous():
+            raise ValueError("klen: a contiguous int32 [B] device tensor")
+        a.klen = klen.data_ptr()
     if drop is not None:
         a.drop = L.drop(drop, q.device)
     if mask is not None:
@@ -394,8 +398,11 @@ def window_geometry(dims, window):
 
 
 def wattn_fwd(q, k, v, ld_qkv, dims, window, full_window, shift, heads, hd, scale, rpb=None, pads=None,
-              out=None, need_lse=True, mask=None, use_table=True, return_table=False, tab=None, drop=None):
+              out=None, need_lse=True, mask=None, use_table=True, return_table=False, tab=None, drop=None,
+              klen=None):
     """Token-major window attention core; returns (out [rows, heads*hd], lse[, tab]).
+    klen: int32 [B] device tensor of valid tokens per clip (one whole-clip window, no bias: dfk.h); rows past it
+    come out as zero.
     use_table: bf16 score-bias tables (RPB + shift mask per shift class, built by dfk_wattn_table, or
     `tab` from an earlier call with the same geometry and rpb); the backward must get the same `tab`."""
     rows = dims[0] * dims[1] * dims[2] * dims[3]
@@ -404,7 +411,7 @@ def wattn_fwd(q, k, v, ld_qkv, dims, window, full_window, shift, heads, hd, scal
     nW, N, Np = window_geometry(dims, window)
     lse = torch.empty(dims[0] * nW * heads, Np, device=q.device, dtype=torch.float32) if need_lse else None
     a = wattn_args(q, k, v, out, ld_qkv, dims, window, full_window, shift, heads, hd, scale, rpb, pads, lse, mask,
-                   drop)
+                   drop, klen)
     if tab is not None:
         a.tab = tab.data_ptr()
     elif use_table:
@@ -437,13 +444,13 @@ def wattn_bwd_policy(group=0, version=-1):
 
 
 def wattn_bwd(fwd_args_tensors, dout, dq, dk, dv, ld_dqkv, drpb=None, dpads=None, mask=None, tab=None, drop=None,
-              dscore=None):
+              dscore=None, klen=None):
     """Backward of wattn_fwd.  fwd_args_tensors = (q, k, v, out, lse, ld_qkv, dims, window, full_window,
     shift, heads, hd, scale, rpb, pads).  dq/dk/dv may alias column slices of one [rows, 3C] buffer."""
     (q, k, v, out, lse, ld_qkv, dims, window, full_window, shift, heads, hd, scale, rpb, pads) = fwd_args_tensors
     ba = L.WattnBwdArgs()
     ba.f = wattn_args(q, k, v, out, ld_qkv, dims, window, full_window, shift, heads, hd, scale, rpb, pads, lse, mask,
-                      drop)
+                      drop, klen)
     if tab is not None:
         ba.f.tab = tab.data_ptr()
     ba.dout = dout.data_ptr()
@@ -548,6 +555,41 @@ def rowmean(x, groups, out_f32=True):
     L.check(L.lib().dfk_rowmean(L.ptr(x), L.ptr(out), groups, R, C, L.dt(x), int(out.dtype == torch.float32),
                                 L.stream()), "rowmean")
     return out
+
+
+def _flen(flen, B):
+    if flen.dtype != torch.int64 or flen.shape != (B,) or not flen.is_cuda or not flen.is_contiguous():
+        raise ValueError("lengths: a contiguous int64 [B] device tensor")
+    return L.ptr(flen)
+
+
+def row_mask(x, flen, out=None):
+    """x [B, T, C]: rows t >= flen[b] (device int64 [B], clamped to [1, T]) zeroed by a select; out may be x."""
+    B, T, C = x.shape
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    L.check(L.lib().dfk_row_mask(L.ptr(x), L.ptr(out), _flen(flen, B), B, T, C, L.dt(x), L.stream()), "row_mask")
+    return out
+
+
+def rowmean_ragged(x, flen):
+    """x [B, T, C] -> fp32 [B, C] mean over t < flen[b]."""
+    B, T, C = x.shape
+    x = x.contiguous()
+    out = torch.empty(B, C, device=x.device, dtype=torch.float32)
+    L.check(L.lib().dfk_rowmean_ragged_fwd(L.ptr(x), L.ptr(out), _flen(flen, B), B, T, C, L.dt(x), L.stream()),
+            "rowmean_ragged_fwd")
+    return out
+
+
+def rowmean_ragged_bwd(dy, flen, T, dtype):
+    """dy fp32 [B, C] -> dx [B, T, C] (dtype): dy / flen[b] on the rows t < flen[b], zero behind them."""
+    B, C = dy.shape
+    dx = torch.empty(B, T, C, device=dy.device, dtype=dtype)
+    L.check(L.lib().dfk_rowmean_ragged_bwd(L.ptr(dy.contiguous()), L.ptr(dx), _flen(flen, B), B, T, C, L.dt(dx),
+                                           L.stream()), "rowmean_ragged_bwd")
+    return dx
 
 
 def w2v_conv0_fwd(wave, w, gamma, beta, eps, dtype):
@@ -659,10 +701,15 @@ def frame_normalize(frames_u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.
     return out
 
 
-def wave_normalize(wave, eps=1e-7):
-    """[B, S] fp32 (zero-padded rows) -> per-row (x - mean) / sqrt(var + eps)."""
+def wave_normalize(wave, eps=1e-7, lengths=None):
+    """[B, S] fp32 (zero-padded rows) -> per-row (x - mean) / sqrt(var + eps).  lengths (device int64 [B]): the
+    statistics over each row's own samples, zeros behind them (the padding is not read)."""
     x = wave.float().contiguous()
     out = torch.empty_like(x)
+    if lengths is not None:
+        L.check(L.lib().dfk_wave_normalize_ragged(L.ptr(x), L.ptr(out), _flen(lengths, x.shape[0]), x.shape[0],
+                                                  x.shape[1], float(eps), L.stream()), "wave_normalize_ragged")
+        return out
     L.check(L.lib().dfk_wave_normalize(L.ptr(x), L.ptr(out), x.shape[0], x.shape[1], float(eps), L.stream()),
             "wave_normalize")
     return out
@@ -909,11 +956,18 @@ def layerdrop_flags(drop, keep, used):
                                         L.stream()), "layerdrop_flags")
 
 
-def spec_augment_fwd(h, embed, mask_prob, mask_length, min_masks, drop):
-    """h [B, T, C] -> (masked copy, mask [B, T] uint8)."""
+def spec_augment_fwd(h, embed, mask_prob, mask_length, min_masks, drop, flen=None):
+    """h [B, T, C] -> (masked copy, mask [B, T] uint8).  flen (device int64 [B]): the ragged form, spans inside each
+    clip's own frames."""
     B, T, C = h.shape
     out = torch.empty_like(h)
     mask = torch.empty(B, T, device=h.device, dtype=torch.uint8)
+    if flen is not None:
+        L.check(L.lib().dfk_spec_augment_ragged_fwd(L.ptr(h), L.ptr(out), L.ptr(mask), L.ptr(embed), _flen(flen, B), B,
+                                                    T, C, float(mask_prob), int(mask_length), int(min_masks),
+                                                    L.drop(drop, h.device), L.dt(h), L.stream()),
+                "spec_augment_ragged_fwd")
+        return out, mask
     L.check(L.lib().dfk_spec_augment_fwd(L.ptr(h), L.ptr(out), L.ptr(mask), L.ptr(embed), B, T, C, float(mask_prob),
                                          int(mask_length), int(min_masks), L.drop(drop, h.device), L.dt(h),
                                          L.stream()), "spec_augment_fwd")

@@ -79,6 +79,8 @@ class FusionModel(nn.Module):
         parallel_branches they run on three HIP streams (video / mel / waveform), so the small-M
         GEMMs of the mel and wav2vec2 trunks fill the CUs the HBM-bound video trunk leaves idle; the
         autograd engine runs each backward op on its forward op's stream, so backward overlaps too."""
+        if len(feature) == 4:   # (video, mel, wave, lengths): the waveform slot's padded batch with its lengths
+            feature = (feature[0], feature[1], (feature[2], feature[3]))
         video_feat, audio_feat, paudio_feat = feature
         if not (self.parallel_branches and video_feat.is_cuda):
             return self.head(self.vExtract(video_feat), self.aExtract(audio_feat), self.paExtract(paudio_feat))
@@ -88,7 +90,8 @@ class FusionModel(nn.Module):
         for s, ext, x in zip(self.branch_streams(), (self.vExtract, self.aExtract, self.paExtract), feature):
             s.wait_stream(cur)
             if not capturing:
-                x.record_stream(s)
+                for t in (x if isinstance(x, tuple) else (x,)):
+                    t.record_stream(s)
             with torch.cuda.stream(s):
                 outs.append(ext(x))
         for s, o in zip(self._streams, outs):

@@ -9,7 +9,9 @@ from ..utils import Mlp
 class Audio2D(nn.Module):
     """wav_model(x).last_hidden_state -> mean over frames (AdaptiveAvgPool2d((1,in_feat)))
     -> F.dropout(p=args.swin_drop) — always on, as the reference (Q9) -> [B, in_feat]
-    fp32 (use_feat=True); or the classifier branch (use_feat=False)."""
+    fp32 (use_feat=True); or the classifier branch (use_feat=False).  Padded batches: lengths= (or x as the pair
+    (wave, lengths), the form a flat feature tuple carries) goes to the wav2vec2 model, and the mean runs over each
+    clip's own frames."""
 
     def __init__(self, args, wav_model, in_feat=768, num_classes=2, use_feat=False):
         super().__init__()
@@ -23,10 +25,18 @@ class Audio2D(nn.Module):
             self.act = nn.GELU()
             self.classify_drop = args.classify_drop
 
-    def forward(self, x, mask=None):
-        h = self.wav_model(x)["last_hidden_state"]
-        B, T, C = h.shape
-        feat = Fn.RowMeanFn.apply(h.reshape(B * T, C), B)
+    def forward(self, x, mask=None, lengths=None):
+        if isinstance(x, (tuple, list)):
+            x, lengths = x
+        if lengths is None:
+            h = self.wav_model(x)["last_hidden_state"]
+            B, T, C = h.shape
+            feat = Fn.RowMeanFn.apply(h.reshape(B * T, C), B)
+        else:
+            from .wav2vec2 import frame_lengths
+            n = self.wav_model.sample_lengths(x, lengths)
+            h = self.wav_model(x, lengths=n)["last_hidden_state"]
+            feat = Fn.RowMeanRaggedFn.apply(h, frame_lengths(n, self.wav_model.config))
         if self.model_drop > 0:
             feat = F.dropout(feat, self.model_drop)
         if not self.use_feat:

@@ -50,6 +50,14 @@ def _w2v_config_path(args, default=W2V_CONFIG):
     return getattr(args, "w2v_config", None) or default
 
 
+def check_paudio_lengths(args, wcfg):
+    """--paudio_lengths needs the layer-norm / pre-norm family (the group-norm conv0 runs over the whole padded row):
+    fail at start-up, not at the first batch."""
+    if getattr(args, "paudio_lengths", False) and not (wcfg.feat_extract_norm == "layer" and wcfg.do_stable_layer_norm):
+        raise ValueError("--paudio_lengths needs a layer-norm --w2v_config (e.g. deepfake_amd/models/"
+                         "w2v_large_config.json); the wav2vec2-base family has no padded-batch path")
+
+
 def build_fused(cfg, args=None, w2v_config=None, compute_dtype=torch.float32, regularize=False, fp8=False):
     """The north-star fused model.  The waveform slot's checkpoint family comes from w2v_config, else from
     args.w2v_config (--w2v_config), else the wav2vec2-base JSON.  regularize=False (parity / default): every dropout, DropPath,
@@ -67,6 +75,7 @@ def build_fused(cfg, args=None, w2v_config=None, compute_dtype=torch.float32, re
     vst = SwinTransformer3D(**vkw)
     mel = SwinTransformerV2(**mkw)
     wcfg = Wav2Vec2Config.from_json_file(w2v_config or _w2v_config_path(args), num_hidden_layers=cfg["w2v_layers"])
+    check_paudio_lengths(args, wcfg)
     if not regularize:
         wcfg = wcfg.deterministic()
     pa = Audio2D(args, Wav2Vec2Model(wcfg), in_feat=wcfg.hidden_size, num_classes=1, use_feat=True)
@@ -109,6 +118,7 @@ def build_model(args, compute_dtype=torch.float32):
         return set_compute_dtype(SwinTransformerV2(**mkw), compute_dtype)
     if args.modality == "paudio":
         wcfg = Wav2Vec2Config.from_json_file(_w2v_config_path(args), num_hidden_layers=cfg["w2v_layers"])
+        check_paudio_lengths(args, wcfg)
         if not reg:
             wcfg = wcfg.deterministic()
         return set_compute_dtype(Audio2D(args, Wav2Vec2Model(wcfg), in_feat=wcfg.hidden_size, num_classes=1),

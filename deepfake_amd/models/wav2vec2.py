@@ -27,6 +27,12 @@ a dropped layer still runs (a captured graph cannot branch) but its output is
 discarded (torch.where), its gradients are zero and the fused SGD skips its
 parameters (as torch's SGD skips grad=None).  config.deterministic() turns all
 of them off (the parity setting, Q12).
+
+Padded batches (layer-norm family only): Wav2Vec2Model.forward(wave, lengths=n) gives every clip the result it
+would get alone — frame_lengths() turns the sample counts into frame counts on the device, the hidden states past a
+clip's frames are zeroed before the positional conv and after the encoder's final LayerNorm (Fn.RowMaskFn), every
+layer's attention masks the keys past them (klen), and SpecAugment draws its spans inside them.  The lengths are
+never read on the host, so the step stays capturable.
 """
 import json
 
@@ -79,6 +85,25 @@ class Wav2Vec2Config:
                   "mask_time_prob", "mask_feature_prob"):
             setattr(self, k, 0.0)
         return self
+
+
+def frame_lengths(n, config):
+    """Frames the conv stack gives for n samples (HF _get_feat_extract_output_lengths, :1059-1077):
+    n <- (n - k_i) // s_i + 1 over the layers.  n: an integer tensor (integer torch ops on its device, no host
+    read), a python integer, or a sequence of them (a list comes back)."""
+    if not torch.is_tensor(n) and not isinstance(n, int):
+        return [frame_lengths(int(v), config) for v in n]
+    for k, s in zip(config.conv_kernel, config.conv_stride):
+        n = torch.div(n - k, s, rounding_mode="floor") + 1 if torch.is_tensor(n) else (n - k) // s + 1
+    return n
+
+
+def receptive_field(config):
+    """Samples behind one output frame of the conv stack (400 for the supported kernels and strides)."""
+    r = 1
+    for k, s in zip(reversed(config.conv_kernel), reversed(config.conv_stride)):
+        r = (r - 1) * s + k
+    return r
 
 
 class _ConvLayer(nn.Module):
@@ -202,16 +227,17 @@ class Wav2Vec2Attention(nn.Module):
         q, k, v = self.q_proj, self.k_proj, self.v_proj
         return [[q.weight, k.weight, v.weight], [q.bias, k.bias, v.bias]]
 
-    def core(self, x, B, T, skip=False):
+    def core(self, x, B, T, skip=False, klen=None):
         """x [B*T, C] -> attention output [B*T, C] before out_proj (skip=True: and an alias of x for the
-        layer's residual, whose gradient joins the q/k/v dX GEMM)."""
+        layer's residual, whose gradient joins the q/k/v dX GEMM).  klen: int32 [B] device tensor of each clip's
+        frames (padded batches): keys past them are masked, rows past them come out as zero."""
         q, k, v = self.q_proj, self.k_proj, self.v_proj
         qkv = Fn.linear_group(x, (q.weight, k.weight, v.weight), (q.bias, k.bias, v.bias), skip=skip)
         if skip:
             qkv, xs = qkv
         geo = ((B, 1, 1, T), (1, 1, T), (1, 1, T), (0, 0, 0), self.num_heads, self.head_dim, self.scaling)
         d = self.dropout.spec() if self.dropout.active(self.training) else None
-        out = Fn.window_attention(qkv, None, None, geo, drop=d)
+        out = Fn.window_attention(qkv, None, None, geo, drop=d, klen=klen)
         return (out, xs) if skip else out
 
 
@@ -290,13 +316,13 @@ class Wav2Vec2Encoder(nn.Module):
         x = Fn.layer_norm(self.pos_conv_embed.add_to(h.contiguous()), self.layer_norm, drop=d).reshape(B * T, C)
         return self._run_layers(x, B, T).view(B, T, C)
 
-    def _run_layers(self, x, B, T):
-        """The layers on x [B*T, C] under LayerDrop (HF/:700-706)."""
+    def _run_layers(self, x, B, T, klen=None):
+        """The layers on x [B*T, C] under LayerDrop (HF/:700-706); klen: the pre-LN layers' key lengths."""
         lds = self.layerdrop.active(self.training)
         if lds:
             K.layerdrop_flags(self.layerdrop.spec(), self.layer_keep, self.layer_used)
         for i, layer in enumerate(self.layers):
-            y = layer(x, B, T)
+            y = layer(x, B, T) if klen is None else layer(x, B, T, klen)
             if not lds:
                 x = y
             elif x.is_cuda and y.dtype == x.dtype and (y.numel() * y.element_size()) % 16 == 0:
@@ -311,12 +337,12 @@ class Wav2Vec2EncoderLayerStableLayerNorm(Wav2Vec2EncoderLayer):
     order, h = h + dropout(out_proj(attn(layer_norm(h)))); h = h + FF(final_layer_norm(h)).  Each residual reads
     its LayerNorm's skip alias, so h's two gradients meet inside the LN backward (as the Swin pre-norm blocks)."""
 
-    def forward(self, x, B, T):
+    def forward(self, x, B, T, klen=None):
         tr = self.training
         ff = self.feed_forward
         spec = lambda d: d.spec() if d.active(tr) else None   # noqa: E731
         xn, xs = Fn.layer_norm(x, self.layer_norm, skip=True)
-        a = self.attention.core(xn, B, T)
+        a = self.attention.core(xn, B, T, klen=klen)
         x = Fn.linear(a, self.attention.out_proj.weight, self.attention.out_proj.bias, residual=xs,
                       drop=spec(self.dropout))
         xn, xs = Fn.layer_norm(x, self.final_layer_norm, skip=True)
@@ -325,24 +351,32 @@ class Wav2Vec2EncoderLayerStableLayerNorm(Wav2Vec2EncoderLayer):
 
 
 class Wav2Vec2EncoderStableLayerNorm(Wav2Vec2Encoder):
-    """HF/:729-802 (no attention mask: equal-length clips): h + pos_conv(h) -> dropout -> pre-LN layers under
-    LayerDrop -> encoder.layer_norm.  Parameter names, LayerDrop coins and SGD gates as the post-LN encoder."""
+    """HF/:729-802: h + pos_conv(h) -> dropout -> pre-LN layers under LayerDrop -> encoder.layer_norm.  Parameter
+    names, LayerDrop coins and SGD gates as the post-LN encoder.  flen (device int64 [B], padded batches): the
+    frames past a clip's own are zeroed before the positional conv (HF/:761-764) and after the final LayerNorm
+    (HF leaves that LayerNorm's output there), and every layer's attention masks them as keys."""
 
     layer_class = Wav2Vec2EncoderLayerStableLayerNorm
     stable_layer_norm = True
 
-    def forward(self, h):
+    def forward(self, h, flen=None):
         B, T, C = h.shape
+        klen = None
+        if flen is not None:
+            h = Fn.RowMaskFn.apply(h, flen)
+            klen = flen.clamp(1, T).to(torch.int32)
         x = self.pos_conv_embed.add_to(h.contiguous()).reshape(B * T, C)
         if self.dropout.active(self.training):
             x = Fn.DropoutFn.apply(x, self.dropout.spec())
-        return Fn.layer_norm(self._run_layers(x, B, T), self.layer_norm).view(B, T, C)
+        y = Fn.layer_norm(self._run_layers(x, B, T, klen), self.layer_norm).view(B, T, C)
+        return y if flen is None else Fn.RowMaskFn.apply(y, flen)
 
 
 class Wav2Vec2Model(nn.Module):
     """HF/:1244-1380 forward.  config.do_stable_layer_norm picks the encoder (HF/:1255) and
-    config.feat_extract_norm the feature encoder.  Equal-length clips are the supported input: an attention_mask
-    (padded batches, and with it the per-clip normalisation the layer-norm checkpoints expect) raises."""
+    config.feat_extract_norm the feature encoder.  Padded batches come with lengths= (the samples of each clip, an
+    int64 [B] device tensor that is never read on the host, or host integers, which are validated), layer-norm
+    family only; HF's attention_mask argument raises."""
 
     def __init__(self, config):
         super().__init__()
@@ -357,18 +391,48 @@ class Wav2Vec2Model(nn.Module):
         if config.mask_feature_prob > 0.0:
             raise NotImplementedError("SpecAugment feature masking (mask_feature_prob > 0)")
 
-    def _mask_hidden_states(self, h):
-        """HF/:1272-1317 time masking (training, apply_spec_augment, mask_time_prob > 0)."""
+    def _mask_hidden_states(self, h, flen=None):
+        """HF/:1272-1317 time masking (training, apply_spec_augment, mask_time_prob > 0); flen: the spans of each
+        clip inside its own frames."""
         c = self.config
         if not (self.training and c.apply_spec_augment and c.mask_time_prob > 0):
             return h
+        if flen is None:
+            return Fn.SpecAugmentFn.apply(h, self.masked_spec_embed, c.mask_time_prob, c.mask_time_length,
+                                          c.mask_time_min_masks, self.spec_site.spec())
         return Fn.SpecAugmentFn.apply(h, self.masked_spec_embed, c.mask_time_prob, c.mask_time_length,
-                                      c.mask_time_min_masks, self.spec_site.spec())
+                                      c.mask_time_min_masks, self.spec_site.spec(), flen)
 
-    def forward(self, input_values, attention_mask=None, **_):
+    def sample_lengths(self, input_values, lengths):
+        """lengths= of forward() as an int64 [B] tensor on the waveform's device.  A device tensor is checked for
+        shape and dtype only (its values are clamped by the kernels that read them); host integers must lie in
+        [receptive field, S]."""
+        if not (self.config.feat_extract_norm == "layer" and self.config.do_stable_layer_norm):
+            raise NotImplementedError("lengths= (padded batches) with the group-norm / post-LN family: its conv0 "
+                                      "GroupNorm runs over the whole padded row")
+        B, S = input_values.shape
+        if torch.is_tensor(lengths) and lengths.is_cuda:
+            if lengths.dtype != torch.int64 or lengths.shape != (B,):
+                raise ValueError(f"lengths: int64 [{B}] expected, got {lengths.dtype} {tuple(lengths.shape)}")
+            return lengths.contiguous()
+        n = torch.as_tensor(lengths)
+        if n.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8):
+            raise ValueError(f"lengths: integers expected, got {n.dtype}")
+        if n.shape != (B,):
+            raise ValueError(f"lengths: [{B}] expected, got {tuple(n.shape)}")
+        lo = receptive_field(self.config)
+        if int(n.min()) < lo or int(n.max()) > S:
+            raise ValueError(f"lengths: values in [{lo}, {S}] expected, got {n.tolist()}")
+        return n.to(torch.int64).to(input_values.device)
+
+    def forward(self, input_values, attention_mask=None, lengths=None, **_):
         if attention_mask is not None:
-            raise NotImplementedError("attention_mask (padded batches)")
+            raise NotImplementedError("attention_mask (padded batches): pass lengths=")
+        flen = None
+        if lengths is not None:
+            flen = frame_lengths(self.sample_lengths(input_values, lengths), self.config)
         f = self.feature_extractor(input_values)
         h, ext = self.feature_projection(f)
-        h = self._mask_hidden_states(h)
-        return {"last_hidden_state": self.encoder(h), "extract_features": ext}
+        h = self._mask_hidden_states(h, flen)
+        h = self.encoder(h) if flen is None else self.encoder(h, flen)
+        return {"last_hidden_state": h, "extract_features": ext}

@@ -5,7 +5,7 @@ the model in eval mode over the test split, probabilities appended to prediction
 'module.' prefix stripped for single-modality checkpoints (:50-74)."""
 import torch
 
-from .trainer import mel_sample_rate, normalize_wave, pad_longest, prepare_mel, prepare_video
+from .trainer import mel_sample_rate, normalize_wave, pad_longest, padded_wave, prepare_mel, prepare_video, wave_samples
 from .utils import Logger
 
 
@@ -15,6 +15,7 @@ class SubmitCtl:
         self.batch_size = args.batch_size
         self.modality = args.modality
         self.mel_sr = mel_sample_rate(args)
+        self.wave_samples = wave_samples(args)
         self.logger = logger or Logger(None)
         self.log_step = args.log_step
         self.model_s = self.model = model.to(device)
@@ -33,11 +34,15 @@ class SubmitCtl:
         """As Trainer._features in eval mode: the mel slot goes through prepare_mel without augmentation (the
         identity for the normalised image; uint8 images and waveforms become the model's input on the device; a
         list of unequal waveforms takes prepare_mel's ragged path)."""
+        samples = self.wave_samples
         if self.modality == "fused":
-            wave = normalize_wave(pad_longest(feat["PAudio"]).to(self.device))
-            return (prepare_video(feat["Video"], self.device), prepare_mel(feat["Audio"], self.device, sr=self.mel_sr),
-                    wave)
+            video, mel = prepare_video(feat["Video"], self.device), prepare_mel(feat["Audio"], self.device, sr=self.mel_sr)
+            if samples is not None:   # --paudio_lengths, as Trainer._features
+                return (video, mel) + padded_wave(feat["PAudio"], self.device, samples)
+            return (video, mel, normalize_wave(pad_longest(feat["PAudio"]).to(self.device)))
         if self.modality == "paudio":
+            if samples is not None:
+                return padded_wave(feat, self.device, samples)
             return normalize_wave(pad_longest(feat).to(self.device))
         if self.modality == "video":
             return prepare_video(feat, self.device)

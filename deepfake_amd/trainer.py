@@ -35,14 +35,24 @@ from .params import ParamStore
 from .utils import AverageMeter, Logger
 
 
-def pad_longest(waves, return_lengths=False):
+def pad_longest(waves, return_lengths=False, pad_to=None):
     """The processor's padding='longest' (src/trainer.py:258): zero-pad every waveform of the batch to the
-    longest one -> [B, S] fp32 (host).  return_lengths: also the clips' own lengths, int64 [B] (host)."""
+    longest one -> [B, S] fp32 (host).  return_lengths: also the clips' own lengths, int64 [B] (host).  pad_to: pad
+    to this many samples instead (one shape for every batch of unequal clips); no clip may be longer."""
     if torch.is_tensor(waves):
         out = waves.float()
-        return (out, torch.full((out.shape[0],), out.shape[-1], dtype=torch.int64)) if return_lengths else out
+        n = out.shape[-1]
+        if pad_to is not None:
+            if n > pad_to:
+                raise ValueError(f"pad_to={pad_to} is shorter than the batch's {n} samples")
+            out = torch.nn.functional.pad(out, (0, pad_to - n))
+        return (out, torch.full((out.shape[0],), n, dtype=torch.int64)) if return_lengths else out
     arrs = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
     S = max(a.numel() for a in arrs)
+    if pad_to is not None:
+        if S > pad_to:
+            raise ValueError(f"pad_to={pad_to} is shorter than the longest clip's {S} samples")
+        S = int(pad_to)
     out = torch.zeros(len(arrs), S, dtype=torch.float32)
     for i, a in enumerate(arrs):
         out[i, :a.numel()] = a
@@ -51,11 +61,32 @@ def pad_longest(waves, return_lengths=False):
     return out
 
 
-def normalize_wave(w):
+def normalize_wave(w, lengths=None):
     """Wav2Vec2FeatureExtractor zero-mean / unit-variance (HF feature_extraction_wav2vec2.py:94-95) of every
-    zero-padded row, whole row included (no attention mask, Q13) — on the GPU (dfk_wave_normalize)."""
+    zero-padded row, whole row included (no attention mask, Q13) — on the GPU (dfk_wave_normalize).  lengths
+    (int64 [B]; moved to w's device): the same with an attention mask (:88-93) — each row's statistics over its own
+    samples, zeros behind them (dfk_wave_normalize_ragged)."""
     from . import kernels as K
-    return K.wave_normalize(w)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int64).to(w.device)
+    return K.wave_normalize(w, lengths=lengths)
+
+
+def padded_wave(waves, device, samples, non_blocking=False):
+    """--paudio_lengths: the waveform slot's input as the pair (wave [B, samples] normalised per clip over its own
+    samples, lengths int64 [B]), both on the device; every batch has the configured clip length's shape."""
+    w, n = pad_longest(waves, return_lengths=True, pad_to=samples)
+    n = n.to(device, non_blocking=non_blocking)
+    return normalize_wave(w.to(device, non_blocking=non_blocking), n), n
+
+
+def wave_samples(args):
+    """The configured clip length in 16 kHz samples (the padded waveform's fixed width under --paudio_lengths), or
+    None with the flag off."""
+    if not getattr(args, "paudio_lengths", False):
+        return None
+    from .models.fused import CONFIGS
+    return int(16000 * CONFIGS[getattr(args, "config", "c2")]["seconds"])
 
 
 def check_finite(loss, step, group=None, device="cpu"):
@@ -449,6 +480,7 @@ class Trainer:
         self.accum_step = max(1, int(args.accum_step))
         self.augment = bool(getattr(args, "augment", False))
         self.mel_sr = mel_sample_rate(args)
+        self.wave_samples = wave_samples(args)   # --paudio_lengths: the waveform slot carries its clips' lengths
         self.dataset = dataset
         self.trainloader = dataset.train_dataloader()
         self.valloader = dataset.val_dataloader()
@@ -543,11 +575,16 @@ class Trainer:
         normalised (the processor), frames normalised when they arrive as decoded uint8.  A mel slot that holds
         a list of unequal waveforms (fusion_collate keeps it one) goes through prepare_mel's ragged path."""
         aug = self.augment and self.model.training
+        samples = getattr(self, "wave_samples", None)   # --paudio_lengths: the padded waveform's fixed width
         if self.modality == "fused":
-            wave = normalize_wave(pad_longest(feat["PAudio"]).to(self.device, non_blocking=True))
-            return (prepare_video(feat["Video"], self.device, aug),
-                    prepare_mel(feat["Audio"], self.device, aug, sr=self.mel_sr), wave)
+            video, mel = prepare_video(feat["Video"], self.device, aug), \
+                prepare_mel(feat["Audio"], self.device, aug, sr=self.mel_sr)
+            if samples is not None:   # one more tensor of the flat tuple: the clips' lengths
+                return (video, mel) + padded_wave(feat["PAudio"], self.device, samples, True)
+            return (video, mel, normalize_wave(pad_longest(feat["PAudio"]).to(self.device, non_blocking=True)))
         if self.modality == "paudio":
+            if samples is not None:
+                return padded_wave(feat, self.device, samples, True)
             return normalize_wave(pad_longest(feat).to(self.device, non_blocking=True))
         if self.modality == "video":
             return prepare_video(feat, self.device, aug)

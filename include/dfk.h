@@ -210,6 +210,12 @@ typedef struct {
   dfk_drop drop;        /* attention-probability dropout (mode 1, bf16 table path only; row = query,
                            col = key of the (clip, window, head) unit): HF eager_attention_forward's
                            nn.functional.dropout(attn_weights, p=attention_dropout) (HF :458) */
+  const int32_t* klen;  /* NULL, or device [B]: valid tokens per clip (a key-padding mask as lengths; wav2vec2's
+                           padded batches).  kn = clamp(klen[b], 1, N): keys >= kn get -inf and their blocks are
+                           skipped, rows >= kn of q / k / v / out / dout never reach arithmetic, rows >= kn of out
+                           (and of dq / dk / dv in the backward) are written as zero.  One window per clip that
+                           covers it exactly (window == (D, H, W)), no rpb, shift, mask or pad_*; the fp32 kernels
+                           and the bf16 no-bias kernels (else DFK_EINVAL).  Read on the device only. */
 } dfk_wattn_args;
 int dfk_wattn_fwd(const dfk_wattn_args* a, hipStream_t stream);
 /* kernel-selection policy of dfk_wattn_fwd's hd-32 table path (process-wide; tests and A/B runs only — the
@@ -581,6 +587,23 @@ int dfk_spec_augment_fwd(const void* h, void* out, uint8_t* mask, const void* em
                          int dtype, hipStream_t stream);
 int dfk_spec_augment_bwd(const void* dy, void* dx, const uint8_t* mask, float* dembed, int32_t B, int32_t T,
                          int32_t C, int dtype, hipStream_t stream);
+/* The ragged form (HF _compute_mask_indices with an attention mask): flen device int64 [B] frames per clip,
+ * Tb = clamp(flen[b], 1, T); clip b's span count comes from Tb and its starts are drawn in [0, Tb - mask_length];
+ * no frame >= Tb is masked (HF's dummy index is not reproduced).  With every Tb == T the draws and the mask are
+ * dfk_spec_augment_fwd's. */
+int dfk_spec_augment_ragged_fwd(const void* h, void* out, uint8_t* mask, const void* embed, const int64_t* flen,
+                                int32_t B, int32_t T, int32_t C, float mask_prob, int32_t mask_length,
+                                int32_t min_masks, const dfk_drop* drop, int dtype, hipStream_t stream);
+/* Row mask of a padded batch: y[b, t, :] = t < clamp(flen[b], 1, T) ? x[b, t, :] : 0 (a select: x there may be
+ * anything); the backward is the same op on the gradient.  C * sizeof(element) % 16 == 0, y may alias x. */
+int dfk_row_mask(const void* x, void* y, const int64_t* flen, int32_t B, int32_t T, int32_t C, int dtype,
+                 hipStream_t stream);
+/* Ragged row mean, out[b][c] = mean over t < Tb of x[b][t][c] (fp32 out, Tb as above), and its backward
+ * dx[b][t][c] = t < Tb ? dy[b][c] / Tb : 0 (dy fp32, dx in dtype). */
+int dfk_rowmean_ragged_fwd(const void* x, float* out, const int64_t* flen, int32_t B, int32_t T, int32_t C, int dtype,
+                           hipStream_t stream);
+int dfk_rowmean_ragged_bwd(const float* dy, void* dx, const int64_t* flen, int32_t B, int32_t T, int32_t C, int dtype,
+                           hipStream_t stream);
 
 /* Frame normalisation on the device: T.ToTensor() + T.Normalize(mean, std) of
  * data/data_process.py:55-69 on decoded RGB frames (src/utils.py:22-39): src uint8 [frames, H, W, 3]
@@ -592,6 +615,11 @@ int dfk_frame_normalize(const uint8_t* src, float* dst, int64_t frames, int32_t 
  * (transformers feature_extraction_wav2vec2.py:94-95, called at src/trainer.py:258) of every row of a
  * zero-padded [B, S] batch (no attention mask, Q13): y = (x - mean) / sqrt(var + eps), eps = 1e-7. */
 int dfk_wave_normalize(const float* x, float* y, int64_t B, int64_t S, float eps, hipStream_t stream);
+/* The same per clip of a padded batch (zero_mean_unit_var_norm with an attention mask, :88-93): with
+ * n = clamp(len[b], 1, S) (len: device int64 [B]), mean and variance over x[b, :n], y[b, :n] normalised and
+ * y[b, n:] = 0.  x[b, n:] is never read. */
+int dfk_wave_normalize_ragged(const float* x, float* y, const int64_t* len, int64_t B, int64_t S, float eps,
+                              hipStream_t stream);
 
 /* ---- media front end on the device (csrc/media.hip) ----
  * Mel-spectrogram image of generate_mel_spectrogram (src/utils.py:63-87): librosa.feature.melspectrogram(y, sr,

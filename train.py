@@ -68,7 +68,9 @@ def train(args, logger):
     data.setup(event)
     # the captured step's inputs have one shape: clips of unequal length (padded waveforms that change from batch
     # to batch) run the eager step
-    graph = args.graph and getattr(args, "audio_seconds_min", None) is None
+    # (--paudio_lengths pads the waveform slot to the configured length, so the paudio modality keeps its graph)
+    fixed = getattr(args, "paudio_lengths", False) and args.modality == "paudio"
+    graph = args.graph and (getattr(args, "audio_seconds_min", None) is None or fixed)
     if args.graph and not graph:
         logger("--audio_seconds_min: waveform lengths vary between batches, running the eager step (no HIP graph)")
     trainer = Trainer(model, args, device, data, logger, processor=None, compute_dtype=dt, graph=graph)
