@@ -10,6 +10,8 @@
   --mel_source {image,uint8,wave,wave16k}   mel slot input: the reference's cached image (fp32 normalised, or
                            the uint8 grey image), a 22.05 kHz waveform, or the clip's own 16 kHz waveform (the same
                            samples wav2vec2 gets), resampled and turned into the mel image on the GPU
+  --audio_seconds FLOAT    clip length of the waveform and mel slots in seconds, in place of the configuration's own
+                           (wav2vec2 attention streams K / V through LDS past 640 frames, so 15 s or 30 s clips run)
   --audio_seconds_min      shortest synthetic clip (seconds): clips of unequal length, each mel image built from its
                            clip's own length on the GPU (default: one fixed length)
   --paudio_lengths         waveform slot with per-clip lengths (layer-norm --w2v_config only): each clip normalised
@@ -100,6 +102,9 @@ def build_parser():
                         help='shortest clip in seconds: every clip draws its own audio length between this and the '
                              "configuration's (unequal clips per batch; the waveform mel sources then build each "
                              "image from its clip's own length).  Default: every clip has the configuration's length")
+    parser.add_argument('--audio_seconds', type=float, default=None,
+                        help="clip length in seconds of the waveform and mel slots (e.g. 30); default: the "
+                             "configuration's own.  --audio_seconds_min and the padded width of --paudio_lengths follow")
     parser.add_argument('--paudio_lengths', action='store_true',
                         help="waveform slot: pass every clip's own length to wav2vec2 (per-clip normalisation, key "
                              'padding mask, pooling over the clip\'s frames); needs a layer-norm --w2v_config')
@@ -133,12 +138,23 @@ def get_opt(argv=None):
     return build_parser().parse_args(argv)
 
 
+def audio_seconds(args, cfg):
+    """The clip length in seconds: --audio_seconds, or the configuration's own."""
+    sec = getattr(args, "audio_seconds", None)
+    if sec is None:
+        return cfg["seconds"]
+    if not sec > 0:
+        raise ValueError(f"--audio_seconds must be positive, got {sec}")
+    return int(sec) if float(sec).is_integer() else float(sec)
+
+
 def clip_seconds(args, cfg):
-    """The synthetic clips' audio length for deepfake_amd.data.DeepFake: the configuration's fixed length, or with
-    --audio_seconds_min the pair (lo, hi) from which every clip draws its own."""
+    """The synthetic clips' audio length for deepfake_amd.data.DeepFake: the fixed length (--audio_seconds, or the
+    configuration's), or with --audio_seconds_min the pair (lo, hi) from which every clip draws its own."""
+    hi = audio_seconds(args, cfg)
     lo = getattr(args, "audio_seconds_min", None)
     if lo is None:
-        return cfg["seconds"]
-    if not 0 < lo <= cfg["seconds"]:
-        raise ValueError(f"--audio_seconds_min must lie in (0, {cfg['seconds']}], got {lo}")
-    return (lo, cfg["seconds"])
+        return hi
+    if not 0 < lo <= hi:
+        raise ValueError(f"--audio_seconds_min must lie in (0, {hi}], got {lo}")
+    return (lo, hi)

@@ -843,6 +843,126 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// One (32-query block, 32-key block) step of the no-bias forward — the arithmetic v3 and v3s share, so that both
+// give the same bits: the -m k-step, the lazy rescale, P = 2^D, the dropout multiplier, V^T P^T and the selector
+// row sums.  kbase / vbase: the key block's K and V tiles in LDS (wherever the caller staged them); kb: the GLOBAL
+// key-block index (kb == 0 starts the running max, kb == nkb - 1 holds the keys >= kn, and the dropout mask is keyed
+// on 32 kb + the key's offset, so the backward regenerates it); o, l4, m, mB: the query block's running state.
+template <int HD, bool DROP>
+__device__ __forceinline__ void fwd3_block(const bf16raw* kbase, const bf16raw* vbase, int kb, int nkb, int kn, int lane,
+                                           const int (&koff)[HD / 16], const int (&vlo)[HD / 32],
+                                           const int (&vhi)[HD / 32], const bf16x8& onesA, const bf16x8& sel,
+                                           const bf16x8 (&qf)[HD / 16], f32x16 (&o)[HD / 32], f32x4& l4, float& m,
+                                           bf16x8& mB, const DropCtx& dc, long qrow_id) {
+  constexpr int NKK = HD / 16, NOT = HD / 32;
+  const int hh = lane >> 5;
+  // D = K Q'^T - m
+  f32x16 d = mfma32(onesA, mB, f32x16{});
+#pragma unroll
+  for (int kk = 0; kk < NKK; ++kk) d = mfma32(*reinterpret_cast<const bf16x8*>(kbase + koff[kk]), qf[kk], d);
+  if (kb == nkb - 1) {   // keys beyond N, or beyond kn (no table: the only padded key block)
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (kb * 32 + (j & 3) + 8 * (j >> 2) + 4 * hh >= kn) d[j] = -INFINITY;
+  }
+  // lazy rescale: the block max relative to m (lanes l and l^32 hold the same query)
+  float x0 = max3f(d[0], d[1], d[2]), x1 = max3f(d[3], d[4], d[5]), x2 = max3f(d[6], d[7], d[8]);
+  float x3 = max3f(d[9], d[10], d[11]), x4 = max3f(d[12], d[13], d[14]);
+  float bm = max3f(max3f(x0, x1, x2), max3f(x3, x4, d[15]), -INFINITY);
+  const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(bm), __float_as_uint(bm), false, false);
+  bm = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+  const bool grow = kb == 0 || bm > kRescale;
+  if (__builtin_amdgcn_ballot_w64(grow) != 0) {
+    // m' = m + bm rounded up to a bf16 value: every exponent of this block stays <= 0
+    const float mn = grow ? bf16_ceil(m + bm) : m;
+    const float delta = mn - m;
+    const float alpha = kb == 0 ? 0.f : __builtin_amdgcn_exp2f(-delta);
+    m = mn;
+    mB[0] = (__bf16)(hh == 0 ? -m : 0.f);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) d[j] -= delta;
+    // the row sums sit in lanes 0-15 (queries 0-15 in register 0, 16-31 in register 1): their factors
+    const float a0 = __shfl(alpha, lane & 15, 64), a1 = __shfl(alpha, (lane & 15) + 16, 64);
+    l4[0] *= a0;
+    l4[1] *= a1;
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) o[ot][j] *= alpha;
+  }
+  // P = 2^D as the B operand of k-steps c = 0, 1 (registers 8c .. 8c+7)
+  bf16x8 pf[2], pv[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pf[c][j] = (__bf16)__builtin_amdgcn_exp2f(d[8 * c + j]);
+  if constexpr (DROP) {   // O accumulates the dropped probabilities, l the undropped ones
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        pv[c][j] = (__bf16)((float)pf[c][j] * drop_mul(dc, qrow_id, kb * 32 + 16 * c + 8 * (j >> 2) + 4 * hh + (j & 3)));
+  } else {
+    pv[0] = pf[0];
+    pv[1] = pf[1];
+  }
+  // O^T += V^T P^T: A operand rows e = 32 ot + r, k-step c slots 8 hh + j <-> keys 16 c + 8 (j>>2) + 4 hh + (j&3)
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot) {
+      const bf16x8 va = tr16x2(vbase + c * 16 * HD + vlo[ot], vbase + c * 16 * HD + vhi[ot]);
+      o[ot] = mfma32(va, pv[c], o[ot]);
+    }
+    l4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sel, pf[c], l4, 0, 0, 0);
+  }
+}
+
+// the zero rows of a 32-query block wholly past kn (klen): out rows and lse 0, no arithmetic
+template <int HD>
+__device__ __forceinline__ void fwd3_zero_block(const dfk_wattn_args& a, const Geo& g, int b, long unit, int hoff, int qb,
+                                                int lane) {
+  const int q = qb * 32 + (lane & 31), hh = lane >> 5;
+  if (q < g.N) {
+    bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff + hh * (HD / 2);
+#pragma unroll
+    for (int c = 0; c < HD / 16; ++c) *reinterpret_cast<uint4*>(op + 8 * c) = make_uint4(0, 0, 0, 0);
+    if (a.lse && hh == 0) a.lse[unit * g.Np + q] = 0.f;
+  }
+}
+
+// the end of a query block: O = O^T / l and lse = (m + log2 l) ln 2; rows >= kn of the block that holds kn are zero
+template <int HD, bool KL>
+__device__ __forceinline__ void fwd3_store(const dfk_wattn_args& a, const Geo& g, int b, long unit, int hoff, int qb,
+                                           int kn, int qrow, int lane, const f32x16 (&o)[HD / 32], const f32x4& l4,
+                                           float m) {
+  constexpr int NOT = HD / 32;
+  const int r = lane & 31, hh = lane >> 5;
+  // lane holds e = 32 ot + (j & 3) + 8 (j >> 2) + 4 hh of query r
+  const float l = selsum(l4, lane);
+  const float inv = 1.f / l;
+  if (qrow >= 0) {
+    bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + (long)qrow * a.ld_out + hoff;
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+      for (int jg = 0; jg < 4; ++jg) {
+        uint2 u;
+        u.x = (uint32_t)f2bf(o[ot][4 * jg] * inv) | ((uint32_t)f2bf(o[ot][4 * jg + 1] * inv) << 16);
+        u.y = (uint32_t)f2bf(o[ot][4 * jg + 2] * inv) | ((uint32_t)f2bf(o[ot][4 * jg + 3] * inv) << 16);
+        *reinterpret_cast<uint2*>(op + ot * 32 + 8 * jg + 4 * hh) = u;
+      }
+  }
+  const int q = qb * 32 + r;
+  if (KL && q >= kn && q < g.N) {   // a row past kn in the block that holds kn
+    bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff + hh * (HD / 2);
+#pragma unroll
+    for (int c = 0; c < HD / 16; ++c) *reinterpret_cast<uint4*>(op + 8 * c) = make_uint4(0, 0, 0, 0);
+  }
+  if (a.lse && hh == 0 && q < g.N)
+    a.lse[unit * g.Np + q] = (KL && q >= kn) ? 0.f : (m + __log2f(l)) * 0.6931471805599453f;
+}
+
 // Forward v3 (no score bias at all: wav2vec2; the bias-table forms are v4 and v6).  One workgroup = one (clip,
 // window, head) (x qsplit), 4 waves; K and V of the window staged once in XOR-swizzled LDS tiles.  Per wave and
 // 32-query block, per 32-key block:
@@ -929,13 +1049,7 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
   load_q(min(wu.qpart * nw + wave, nqb - 1));
   for (int qb = wu.qpart * nw + wave; qb < nqb; qb += qstep) {
     if (KL && qb * 32 >= kn) {   // a query block wholly past kn: zero rows, no arithmetic (so are all the later ones)
-      const int q = qb * 32 + r;
-      if (q < g.N) {
-        bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff + hh * (HD / 2);
-#pragma unroll
-        for (int c = 0; c < HD / 16; ++c) *reinterpret_cast<uint4*>(op + 8 * c) = make_uint4(0, 0, 0, 0);
-        if (a.lse && hh == 0) a.lse[unit * g.Np + q] = 0.f;
-      }
+      fwd3_zero_block<HD>(a, g, b, unit, hoff, qb, lane);
       continue;
     }
     const int qrow = qrown;
@@ -956,96 +1070,153 @@ __global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3_k
     for (int ot = 0; ot < NOT; ++ot)
 #pragma unroll
       for (int j = 0; j < 16; ++j) o[ot][j] = 0.f;
-    auto block = [&](int kb) {
-      const bf16raw* kbase = Ks + kb * 32 * HD;
-      const bf16raw* vbase = Vs + kb * 32 * HD;
-      // D = K Q'^T + bias' - m
-      f32x16 d = mfma32(onesA, mB, f32x16{});
-#pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) d = mfma32(*reinterpret_cast<const bf16x8*>(kbase + koff[kk]), qf[kk], d);
-      if (kb == nkb - 1) {   // keys beyond N, or beyond kn (no table: the only padded key block)
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          if (kb * 32 + (j & 3) + 8 * (j >> 2) + 4 * hh >= kn) d[j] = -INFINITY;
-      }
-      // lazy rescale: the block max relative to m (lanes l and l^32 hold the same query)
-      float x0 = max3f(d[0], d[1], d[2]), x1 = max3f(d[3], d[4], d[5]), x2 = max3f(d[6], d[7], d[8]);
-      float x3 = max3f(d[9], d[10], d[11]), x4 = max3f(d[12], d[13], d[14]);
-      float bm = max3f(max3f(x0, x1, x2), max3f(x3, x4, d[15]), -INFINITY);
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(bm), __float_as_uint(bm), false, false);
-      bm = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      const bool grow = kb == 0 || bm > kRescale;
-      if (__builtin_amdgcn_ballot_w64(grow) != 0) {
-        // m' = m + bm rounded up to a bf16 value: every exponent of this block stays <= 0
-        const float mn = grow ? bf16_ceil(m + bm) : m;
-        const float delta = mn - m;
-        const float alpha = kb == 0 ? 0.f : __builtin_amdgcn_exp2f(-delta);
-        m = mn;
-        mB[0] = (__bf16)(hh == 0 ? -m : 0.f);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) d[j] -= delta;
-        // the row sums sit in lanes 0-15 (queries 0-15 in register 0, 16-31 in register 1): their factors
-        const float a0 = __shfl(alpha, lane & 15, 64), a1 = __shfl(alpha, (lane & 15) + 16, 64);
-        l4[0] *= a0;
-        l4[1] *= a1;
-#pragma unroll
-        for (int ot = 0; ot < NOT; ++ot)
-#pragma unroll
-          for (int j = 0; j < 16; ++j) o[ot][j] *= alpha;
-      }
-      // P = 2^D as the B operand of k-steps c = 0, 1 (registers 8c .. 8c+7)
-      bf16x8 pf[2], pv[2];
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[c][j] = (__bf16)__builtin_amdgcn_exp2f(d[8 * c + j]);
-      if constexpr (DROP) {   // O accumulates the dropped probabilities, l the undropped ones
-        const long qrow_id = unit * g.Np + qb * 32 + r;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            pv[c][j] = (__bf16)((float)pf[c][j] * drop_mul(dc, qrow_id, kb * 32 + 16 * c + 8 * (j >> 2) + 4 * hh + (j & 3)));
-      } else {
-        pv[0] = pf[0];
-        pv[1] = pf[1];
-      }
-      // O^T += V^T P^T: A operand rows e = 32 ot + r, k-step c slots 8 hh + j <-> keys 16 c + 8 (j>>2) + 4 hh + (j&3)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-#pragma unroll
-        for (int ot = 0; ot < NOT; ++ot) {
-          const bf16x8 va = tr16x2(vbase + c * 16 * HD + vlo[ot], vbase + c * 16 * HD + vhi[ot]);
-          o[ot] = mfma32(va, pv[c], o[ot]);
-        }
-        l4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sel, pf[c], l4, 0, 0, 0);
-      }
-    };
-    for (int kb = 0; kb < nkb; ++kb) block(kb);
-    // O = O^T / l: lane holds e = 32 ot + (j & 3) + 8 (j >> 2) + 4 hh of query r
-    const float l = selsum(l4, lane);
-    const float inv = 1.f / l;
-    if (qrow >= 0) {
-      bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + (long)qrow * a.ld_out + hoff;
-#pragma unroll
-      for (int ot = 0; ot < NOT; ++ot)
-#pragma unroll
-        for (int jg = 0; jg < 4; ++jg) {
-          uint2 u;
-          u.x = (uint32_t)f2bf(o[ot][4 * jg] * inv) | ((uint32_t)f2bf(o[ot][4 * jg + 1] * inv) << 16);
-          u.y = (uint32_t)f2bf(o[ot][4 * jg + 2] * inv) | ((uint32_t)f2bf(o[ot][4 * jg + 3] * inv) << 16);
-          *reinterpret_cast<uint2*>(op + ot * 32 + 8 * jg + 4 * hh) = u;
-        }
-    }
-    const int q = qb * 32 + r;
-    if (KL && q >= kn && q < g.N) {   // a row past kn in the block that holds kn
-      bf16raw* op = reinterpret_cast<bf16raw*>(a.out) + ((long)b * g.N + q) * a.ld_out + hoff + hh * (HD / 2);
-#pragma unroll
-      for (int c = 0; c < HD / 16; ++c) *reinterpret_cast<uint4*>(op + 8 * c) = make_uint4(0, 0, 0, 0);
-    }
-    if (a.lse && hh == 0 && q < g.N)
-      a.lse[unit * g.Np + q] = (KL && q >= kn) ? 0.f : (m + __log2f(l)) * 0.6931471805599453f;
+    const long qrow_id = unit * g.Np + qb * 32 + r;   // the dropout mask's row
+    for (int kb = 0; kb < nkb; ++kb)
+      fwd3_block<HD, DROP>(Ks + kb * 32 * HD, Vs + kb * 32 * HD, kb, nkb, kn, lane, koff, vlo, vhi, onesA, sel, qf, o, l4, m,
+                           mB, dc, qrow_id);
+    fwd3_store<HD, KL>(a, g, b, unit, hoff, qb, kn, qrow, lane, o, l4, m);
   }
+}
+
+// Forward v3s (v3 for clips whose K and V do not fit LDS; dfk_wattn_fwd_policy version 7 runs it at every size): the
+// query blocks stay resident, K and V stream.  One workgroup = 4 consecutive 32-query blocks of one (clip, head)
+// unit (grid.y covers them), one per wave: the wave keeps its block's o[], l4, m and mB in registers for the whole
+// launch and runs fwd3_block over every key block in v3's order, so out and lse are v3's bits.  K and V pass through
+// LDS in chunks of kF3sKC key blocks, in v3's swizzled tile layout (the swizzle depends on the row's low 4 bits only,
+// so a chunk-local row indexes it like the global one), double-buffered: the next chunk's global loads are issued
+// before the current chunk's arithmetic and written to the other buffer after it, one barrier per chunk.
+// kF3sKC = 4 (128 keys): 2 buffers x (K + V) x 128 rows = 64 KiB at hd 64, 32 KiB at hd 32, so two workgroups share a
+// CU's 160 KiB at hd 64 — the 2 waves / SIMD that v3's register footprint (161-181 VGPRs at hd 64; v3s: 189-211) allows anyway; 256
+// keys would leave one workgroup (one wave / SIMD) per CU at hd 64, with nothing to cover the barrier.  A chunk is
+// 4 (hd 64) or 2 (hd 32) 16-B pieces of K and of V per thread, v3's staging batch.
+// klen: chunks wholly past kn are neither staged nor run, rows >= kn of the last live chunk are staged as zero and
+// scored -inf (fwd3_block), query blocks wholly past kn write zero rows and stage with the others.
+// Resources (kernel-resource-usage, gfx950; VGPRs / SGPRs / LDS per workgroup):
+//   <HD, DROP, KL>    VGPRs  SGPRs  waves/SIMD  dynamic LDS      <HD, DROP, KL>    VGPRs  SGPRs  waves/SIMD  dynamic LDS
+//   <32, no,  no >     116    106       4         32 KiB         <64, no,  no >     211    106       2         64 KiB
+//   <32, no,  yes>     119    106       4         32 KiB         <64, no,  yes>     211    106       2         64 KiB
+//   <32, yes, no >     143    106       3         32 KiB         <64, yes, no >     189    106       2         64 KiB
+//   <32, yes, yes>     145    106       3         32 KiB         <64, yes, yes>     189    104       2         64 KiB
+// (scratch 0 bytes / lane and no VGPR spills in all eight; 8-32 SGPRs of gather geometry are parked in VGPR lanes
+// and read back in the per-chunk staging code, none inside the key-block loop)
+constexpr int kF3sKC = 4;
+
+template <int HD, bool DROP, bool KL = false>
+__global__ __launch_bounds__(256, (HD == 32 && !DROP) ? 3 : 2) void wattn_fwd3s_kernel(const dfk_wattn_args a, const Geo g, int /* qsplit: grid.y */,
+                                                         const bf16raw* __restrict__ /* the table kernels' launch signature */) {
+  constexpr int NKK = HD / 16, NOT = HD / 32, CH = HD / 8, KC = kF3sKC;
+  constexpr int TILE = KC * 32 * HD;            // elements of one chunk of K (or V)
+  constexpr int PCS = KC * 32 * CH;             // its 16-B pieces
+  constexpr int PER = PCS / 256;                // pieces per thread
+  static_assert(PCS % 256 == 0, "a chunk is a whole number of pieces per thread");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16raw* Kb = reinterpret_cast<bf16raw*>(smem);   // [2][TILE]
+  bf16raw* Vb = Kb + 2 * TILE;                      // [2][TILE]
+  const int tid = dfk_tid(), lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, hh = lane >> 5, g16 = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
+  const WUnit wu = decode_unit(a, g, 1);
+  const int head = wu.head, win = wu.win, b = wu.b;
+  const long unit = wu.lse_unit;
+  const int hoff = head * HD;
+  const int kn = key_len<KL>(a, g, b);
+  const int nkb = KL ? (kn + 31) / 32 : g.Np / 32, nqb = g.Np / 32;
+  const int nch = (nkb + KC - 1) / KC;
+  const int qb0 = dfk_bid_y() * 4, qb = qb0 + wave;
+  if (KL && qb0 * 32 >= kn) {   // every block of this workgroup is past kn: zero rows, nothing staged
+    if (qb < nqb) fwd3_zero_block<HD>(a, g, b, unit, hoff, qb, lane);
+    return;
+  }
+  const bool past = KL && qb * 32 >= kn;
+  const bool live = qb < nqb && !past;   // per wave; the others only stage
+  if (qb < nqb && past) fwd3_zero_block<HD>(a, g, b, unit, hoff, qb, lane);
+  // Q'^T B operands of query 32 qb + r: elements 8 hh + j of each 16-wide k-step
+  const int q = min(qb, nqb - 1) * 32 + r;
+  const int qrow = q < kn ? token_info_row(a, g, b, win, q) : -2;
+  bf16x8 qfn[NKK];
+#pragma unroll
+  for (int kk = 0; kk < NKK; ++kk)
+    qfn[kk] = __builtin_bit_cast(bf16x8, tok_ld16<bf16raw>(a.q, a.pad_q, qrow, a.ld_qkv, hoff + kk * 16 + hh * 8));
+  // K / V of chunk c: every load issued (clamped, branch-free addresses; the mask is applied with the LDS write, so
+  // nothing waits on the loads before it), PER pieces of each per thread
+  const int tot = nkb * 32 * CH;
+  uint4 kv[PER], vv[PER];
+  uint32_t okm[PER];
+  auto issue = [&](int c) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int idx = min(c * PCS + tid + u * 256, tot - 1);
+      const int i = idx / CH, col = (idx % CH) * 8;
+      const int row = KL && i >= kn ? -2 : token_info_row(a, g, b, win, i);
+      bool okk, okv;
+      const bf16raw* kp = tok_src<bf16raw>(a.k, a.pad_k, row, a.ld_qkv, hoff + col, okk);
+      const bf16raw* vp = tok_src<bf16raw>(a.v, a.pad_v, row, a.ld_qkv, hoff + col, okv);
+      kv[u] = *reinterpret_cast<const uint4*>(kp);
+      vv[u] = *reinterpret_cast<const uint4*>(vp);
+      okm[u] = (okk ? 1u : 0u) | (okv ? 2u : 0u);
+    }
+  };
+  auto commit = [&](int c, int buf) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int li = tid + u * 256;   // < PCS: inside the buffer
+      if (c * PCS + li < tot) {
+        const int off = buf * TILE + swz<HD>(li / CH, (li % CH) * 8);
+        const uint32_t mk = (okm[u] & 1u) ? 0xffffffffu : 0u, mv = (okm[u] & 2u) ? 0xffffffffu : 0u;
+        *reinterpret_cast<uint4*>(Kb + off) = make_uint4(kv[u].x & mk, kv[u].y & mk, kv[u].z & mk, kv[u].w & mk);
+        *reinterpret_cast<uint4*>(Vb + off) = make_uint4(vv[u].x & mv, vv[u].y & mv, vv[u].z & mv, vv[u].w & mv);
+      }
+    }
+  };
+  issue(0);
+  const bf16x8 sel = rowsum_sel(lane);
+  const float qs = a.scale * kLog2e;
+  const DropCtx dc = drop_ctx(a.drop);
+  int koff[NKK], vlo[NOT], vhi[NOT];   // as in v3: one offset serves every key block of a tile
+#pragma unroll
+  for (int kk = 0; kk < NKK; ++kk) koff[kk] = swz<HD>(r, kk * 16 + hh * 8);
+#pragma unroll
+  for (int ot = 0; ot < NOT; ++ot) {
+    const int k0 = 4 * (g16 >> 1) + tq, col = ot * 32 + 16 * (g16 & 1) + 4 * tp;
+    vlo[ot] = swz<HD>(k0, col);
+    vhi[ot] = swz<HD>(k0 + 8, col);
+  }
+  bf16x8 onesA;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) onesA[j] = (__bf16)(hh == 0 && j == 0 ? 1.f : 0.f);
+  bf16x8 qf[NKK];
+#pragma unroll
+  for (int kk = 0; kk < NKK; ++kk) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qf[kk][j] = (__bf16)((float)qfn[kk][j] * qs);
+  }
+  f32x16 o[NOT];
+  f32x4 l4 = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = 0.f;
+  bf16x8 mB;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) mB[j] = (__bf16)0.f;
+#pragma unroll
+  for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) o[ot][j] = 0.f;
+  const long qrow_id = unit * g.Np + qb * 32 + r;   // the dropout mask's row
+  commit(0, 0);
+  __syncthreads();
+  for (int c = 0; c < nch; ++c) {
+    const int cur = c & 1;
+    const bool more = c + 1 < nch;
+    if (more) issue(c + 1);
+    if (live) {
+      const int kend = min(nkb, (c + 1) * KC);
+      for (int kb = c * KC; kb < kend; ++kb) {
+        const int lo = cur * TILE + (kb - c * KC) * 32 * HD;
+        fwd3_block<HD, DROP>(Kb + lo, Vb + lo, kb, nkb, kn, lane, koff, vlo, vhi, onesA, sel, qf, o, l4, m, mB, dc, qrow_id);
+      }
+    }
+    if (more) commit(c + 1, cur ^ 1);   // the buffer every wave left at the last barrier
+    __syncthreads();
+  }
+  if (live) fwd3_store<HD, KL>(a, g, b, unit, hoff, qb, kn, qrow, lane, o, l4, m);
 }
 
 // Forward v4 (bias tables): v3's structure with the score bias entering as the C input of the first QK^T MFMA and
@@ -2086,8 +2257,28 @@ extern "C" int dfk_wattn_fwd(const dfk_wattn_args* ap, hipStream_t s) {
     const bool tab = has_bias(a, g);
     const bf16raw* t3 = tab ? tab3_fwd(a, g) : nullptr;
     const size_t lds = 4 * (size_t)g.Np * a.hd;
-    if (lds > 160 * 1024) return DFK_EINVAL;
     const int nqb = g.Np / 32;
+    // no bias and a clip whose K / V image does not fit LDS (640 frames at hd 64, 1280 at hd 32): v3s streams it;
+    // below that v3 stays (profiles/w2v/long_timing.md), unless dfk_wattn_fwd_policy version 7 asks for v3s
+    if (!tab && (lds > 160 * 1024 || g_fwd_version == 7)) {
+      const dim3 grid((unsigned)units, (unsigned)dfk_cdiv(nqb, 4)), block(256);
+      const size_t lds_s = (size_t)8 * kF3sKC * 32 * a.hd;   // 2 buffers x (K + V) x kF3sKC key blocks, bf16
+      const bool drop = a.drop.mode != 0, kl = a.klen != nullptr;
+      if (a.hd == 32) {
+        if (kl && drop) launch_lds<wattn_fwd3s_kernel<32, true, true>>(grid, block, lds_s, s, a, g, 1, t3);
+        else if (kl) launch_lds<wattn_fwd3s_kernel<32, false, true>>(grid, block, lds_s, s, a, g, 1, t3);
+        else if (drop) launch_lds<wattn_fwd3s_kernel<32, true>>(grid, block, lds_s, s, a, g, 1, t3);
+        else launch_lds<wattn_fwd3s_kernel<32, false>>(grid, block, lds_s, s, a, g, 1, t3);
+      } else {
+        if (kl && drop) launch_lds<wattn_fwd3s_kernel<64, true, true>>(grid, block, lds_s, s, a, g, 1, t3);
+        else if (kl) launch_lds<wattn_fwd3s_kernel<64, false, true>>(grid, block, lds_s, s, a, g, 1, t3);
+        else if (drop) launch_lds<wattn_fwd3s_kernel<64, true>>(grid, block, lds_s, s, a, g, 1, t3);
+        else launch_lds<wattn_fwd3s_kernel<64, false>>(grid, block, lds_s, s, a, g, 1, t3);
+      }
+      DFK_CHECK_LAUNCH();
+      return 0;
+    }
+    if (lds > 160 * 1024) return DFK_EINVAL;
     const int qgrp = tab && a.hd == 32 && !a.drop.mode && nqb >= 2 ? kFwdQGroup : 1;
     const int ngrp = dfk_cdiv(nqb, qgrp);
     const int nw = std::min(4, ngrp);

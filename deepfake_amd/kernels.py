@@ -432,7 +432,8 @@ def wattn_fwd_policy(version=-1, bal_min_units=-1):
     """Process-wide kernel choice of the hd-32 bf16 table forward (tests / A/B runs): version 6 (no running max,
     16x16x32 tiles, default), 5 (32x32x16) or 4 (max-subtracted); bal_min_units = smallest launch that runs
     version 5 on its balanced key-split schedule.  -1 leaves a setting, -2 restores the default.  The bias table
-    must be built under the same policy as the forward."""
+    must be built under the same policy as the forward.  Version 7 runs the no-bias bf16 forward (wav2vec2) on the
+    streaming kernel v3s at every size, not only where K / V do not fit LDS; it gives v3's bits."""
     L.check(L.lib().dfk_wattn_fwd_policy(int(version), int(bal_min_units)), "wattn_fwd_policy")
 
 

@@ -81,12 +81,17 @@ def padded_wave(waves, device, samples, non_blocking=False):
 
 
 def wave_samples(args):
-    """The configured clip length in 16 kHz samples (the padded waveform's fixed width under --paudio_lengths), or
-    None with the flag off."""
+    """The configured clip length (--audio_seconds, or the configuration's own) in 16 kHz samples (the padded
+    waveform's fixed width under --paudio_lengths), or None with the flag off."""
     if not getattr(args, "paudio_lengths", False):
         return None
     from .models.fused import CONFIGS
-    return int(16000 * CONFIGS[getattr(args, "config", "c2")]["seconds"])
+    sec = getattr(args, "audio_seconds", None)
+    if sec is None:
+        sec = CONFIGS[getattr(args, "config", "c2")]["seconds"]
+    if not sec > 0:
+        raise ValueError(f"--audio_seconds must be positive, got {sec}")
+    return int(16000 * sec)
 
 
 def check_finite(loss, step, group=None, device="cpu"):

@@ -223,7 +223,11 @@ int dfk_wattn_fwd(const dfk_wattn_args* a, hipStream_t stream);
  * same on 32x32x16 tiles, 4 = the max-subtracted forward; bal_min_units = smallest launch (units = clips x windows
  * x heads) that runs version 5 on its key-split balanced schedule (default 512; version 6 has no such schedule).
  * -1 leaves a setting unchanged, bal_min_units -2 restores its default.  Returns 0.  dfk_wattn_table builds its
- * forward bias tiles in the layout of the version in force, so a table must come from the same policy as the forward that reads it. */
+ * forward bias tiles in the layout of the version in force, so a table must come from the same policy as the forward that reads it.
+ * version 7 = the no-bias bf16 forward (no rpb, shift or mask: wav2vec2) runs the streaming kernel v3s at every
+ * size.  By default (6) v3s runs only where the K / V of one window do not fit LDS (4 Np hd > 160 KiB: past 640
+ * tokens at hd 64, 1280 at hd 32) and v3 below; both give the same out and lse bits.  The bias-table, explicit-mask
+ * and fp32 forwards keep their LDS limits (DFK_EINVAL past them). */
 int dfk_wattn_fwd_policy(int32_t version, int64_t bal_min_units);
 /* backward policy (process-wide; tests and A/B runs only).  group: the bf16 table backward runs `group` windows of
  * one (shift class, head) per workgroup and sums their dS^T into one dRPB scratch slab (0 = automatic: enough
