@@ -39,6 +39,8 @@ def test_linear_fwd_bwd(dt, M, N, Kd):
     assert rel(aux, pre) < tol(dt)
     assert rel(y2, torch.nn.functional.gelu(pre)) < tol(dt)
     dy = torch.randn(M, N, device=DEV, generator=g).to(dt)
+    # bf16: kernels.linear_dx sends a plain dX to torch.matmul (_DX_BLAS), so this line checks hipBLASLt, not our
+    # row-major x k-major kernels; those are checked bit for bit in tests/test_gpu_gemm_exact.py (dma_dx_*, reg_*)
     dx = K.linear_dx(dy, w)
     assert rel(dx, dy.float() @ w.float()) < tol(dt)
     dw = torch.zeros(N, Kd, device=DEV)
