@@ -14,7 +14,8 @@
                            (wav2vec2 attention streams K / V through LDS past 640 frames, so 15 s or 30 s clips run)
   --audio_seconds_min      shortest synthetic clip (seconds): clips of unequal length, each mel image built from its
                            clip's own length on the GPU (default: one fixed length)
-  --paudio_lengths         waveform slot with per-clip lengths (layer-norm --w2v_config only): each clip normalised
+  --paudio_lengths         waveform slot with per-clip lengths (a layer-norm --w2v_config, or the wav2vec2-base one with
+                           masked_group_norm, deepfake_amd/models/w2v_base_masked_config.json): each clip normalised
                            over its own samples, its padding masked in every wav2vec2 attention layer and left out of
                            the pooled feature; the padded waveform keeps the configuration's fixed length
   --bucket_mb              gradient all-reduce bucket size
@@ -107,7 +108,9 @@ def build_parser():
                              "configuration's own.  --audio_seconds_min and the padded width of --paudio_lengths follow")
     parser.add_argument('--paudio_lengths', action='store_true',
                         help="waveform slot: pass every clip's own length to wav2vec2 (per-clip normalisation, key "
-                             'padding mask, pooling over the clip\'s frames); needs a layer-norm --w2v_config')
+                             'padding mask, pooling over the clip\'s frames); needs a layer-norm --w2v_config, or the '
+                             'wav2vec2-base one with per-clip GroupNorm statistics, '
+                             'deepfake_amd/models/w2v_base_masked_config.json')
     parser.add_argument('--augment', action='store_true')
     parser.add_argument('--bucket_dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     parser.add_argument('--bucket_mb', type=float, default=64.0)

@@ -127,6 +127,9 @@ SIGNATURES = {
     "dfk_w2v_conv0_fwd_workspace": [_I64, _I64],
     "dfk_w2v_conv0_bwd": [_VP, _I64, _I64, _VP, _VP, _VP, _F, _VP, _VP, C.c_int, _VP, _I64, _VP, _VP, _VP, _VP],
     "dfk_w2v_conv0_bwd_workspace": [_I64, _I64],
+    "dfk_w2v_conv0_ragged_fwd": [_VP, _I64, _I64, _VP, _VP, _VP, _F, _VP, _VP, C.c_int, _VP, _VP, _VP],
+    "dfk_w2v_conv0_ragged_bwd": [_VP, _I64, _I64, _VP, _VP, _VP, _F, _VP, _VP, C.c_int, _VP, _I64, _VP, _VP, _VP, _VP,
+                                 _VP],
     "dfk_w2v_conv0_ln_fwd": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _F, _VP, _VP, C.c_int, _VP],
     "dfk_w2v_conv0_ln_bwd": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, _VP, _I64, _VP, _VP, _VP, _VP,
                              _VP],

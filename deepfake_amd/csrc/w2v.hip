@@ -7,6 +7,12 @@
 // waveform is 0.26 MB/clip; y is never stored), and the backward likewise.
 // The conv itself is VALU work (10 MACs / output) — the pass is HBM-bound on
 // the 13 MB/clip output (bf16).
+// Padded batches (the RAGGED instantiations, dfk_w2v_conv0_ragged_*): len int64 [B] on the device, clip b holds
+// n_b = clamp(len[b], 1, S) samples and T0_b = clamp((n_b - 10) / 5 + 1, 1, T0) frames of its own (both uniform
+// over a workgroup: blockIdx.y is the clip).  Samples at or past n_b are staged as zero without being loaded, the
+// GroupNorm statistics and the backward's reductions run over t < T0_b with T0_b as the divisor, the rows
+// T0_b <= t < T0 of the output are written as zero and those rows of dout are never read: the clip gets the
+// arithmetic it would get alone, and with every length full the uniform call's.
 #include "common.h"
 
 namespace {
@@ -15,13 +21,20 @@ constexpr int TB = 64;    // time steps per workgroup
 constexpr int CH = 512;   // channels (conv_dim[0])
 constexpr int KW = 10, KS = 5;
 
-// stage the waveform segment of this time block and the conv weights into LDS
-__device__ __forceinline__ void stage(const float* __restrict__ x, const float* __restrict__ w, long S, int b, int t0,
-                                      float* xs, float* ws) {
+// samples and frames of clip b's own; the clamps keep every index these give inside the row
+__device__ __forceinline__ long clip_samples(const int64_t* __restrict__ len, int b, long S) {
+  return (long)min(max(len[b], (int64_t)1), (int64_t)S);
+}
+__device__ __forceinline__ int clip_frames(long n, int T0) { return (int)min(max((n - KW) / KS + 1, 1L), (long)T0); }
+
+// stage the waveform segment of this time block (zero from sample n on: n = S, or the clip's own count) and the
+// conv weights into LDS
+__device__ __forceinline__ void stage(const float* __restrict__ x, const float* __restrict__ w, long S, long n, int b,
+                                      int t0, float* xs, float* ws) {
   const long base = (long)b * S + (long)t0 * KS;
   for (int i = threadIdx.x; i < TB * KS + KW; i += 256) {
     const long j = base + i;
-    xs[i] = ((long)t0 * KS + i < S) ? x[j] : 0.f;
+    xs[i] = ((long)t0 * KS + i < n) ? x[j] : 0.f;
   }
   for (int i = threadIdx.x; i < CH * KW; i += 256) ws[i] = w[i];
   __syncthreads();
@@ -35,13 +48,23 @@ __device__ __forceinline__ float conv_at(const float* xs, const float* ws, int t
 }
 
 // pass 1: per (b, time block, c) partial sum and sum of squares of y -> the partial slab [b][block][c][2]
+// RAGGED: over the clip's own frames; a time block wholly past them writes zero partials (the slab is
+// uninitialised and conv0_stats_sum adds every block)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void conv0_stats(const float* __restrict__ x, const float* __restrict__ w, long S,
-                                                   int T0, float* __restrict__ part) {
+                                                   int T0, float* __restrict__ part, const int64_t* __restrict__ len) {
   __shared__ float xs[TB * KS + KW];
   __shared__ float ws[CH * KW];
   const int b = blockIdx.y, t0 = blockIdx.x * TB;
-  stage(x, w, S, b, t0, xs, ws);
-  const int nt = min(TB, T0 - t0);
+  const long n = RAGGED ? clip_samples(len, b, S) : S;
+  const int Tb = RAGGED ? clip_frames(n, T0) : T0;
+  if (RAGGED && t0 >= Tb) {
+    float* dst = part + ((long)b * gridDim.x + blockIdx.x) * CH * 2;
+    for (int i = threadIdx.x; i < CH * 2; i += 256) dst[i] = 0.f;
+    return;
+  }
+  stage(x, w, S, n, b, t0, xs, ws);
+  const int nt = min(TB, Tb - t0);
   for (int c = threadIdx.x; c < CH; c += 256) {
     float s = 0.f, q = 0.f;
     for (int tl = 0; tl < nt; ++tl) {
@@ -76,45 +99,60 @@ __global__ __launch_bounds__(256) void conv0_stats_sum(const float* __restrict__
 }
 
 // pass 2: out = gelu(gn(y)); one thread per (t, channel pair) -> coalesced channels-last stores
-template <typename T>
+// RAGGED: the rows past the clip's own frames are written as zero
+template <typename T, bool RAGGED>
 __global__ __launch_bounds__(256) void conv0_apply(const float* __restrict__ x, const float* __restrict__ w, long S,
                                                    int T0, const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                   const float* __restrict__ beta, float eps, T* __restrict__ out) {
+                                                   const float* __restrict__ beta, float eps, T* __restrict__ out,
+                                                   const int64_t* __restrict__ len) {
   __shared__ float xs[TB * KS + KW];
   __shared__ float ws[CH * KW];
   __shared__ float mu[CH], rs[CH];
   const int b = blockIdx.y, t0 = blockIdx.x * TB;
-  stage(x, w, S, b, t0, xs, ws);
-  for (int c = threadIdx.x; c < CH; c += 256) {
-    const float s = stats[((long)b * CH + c) * 2], q = stats[((long)b * CH + c) * 2 + 1];
-    const float m = s / T0;
-    mu[c] = m;
-    rs[c] = rsqrtf(fmaxf(q / T0 - m * m, 0.f) + eps);
+  const long n = RAGGED ? clip_samples(len, b, S) : S;
+  const int Tb = RAGGED ? clip_frames(n, T0) : T0;
+  const int nt = max(min(TB, Tb - t0), 0);
+  if (nt > 0) {
+    stage(x, w, S, n, b, t0, xs, ws);
+    for (int c = threadIdx.x; c < CH; c += 256) {
+      const float s = stats[((long)b * CH + c) * 2], q = stats[((long)b * CH + c) * 2 + 1];
+      const float m = s / Tb;
+      mu[c] = m;
+      rs[c] = rsqrtf(fmaxf(q / Tb - m * m, 0.f) + eps);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nt * CH; i += 256) {
+      const int tl = i / CH, c = i % CH;
+      const float y = conv_at(xs, ws, tl, c);
+      const float z = (y - mu[c]) * rs[c] * gamma[c] + beta[c];
+      stf<T>(out + ((long)b * T0 + t0 + tl) * CH + c, (sizeof(T) == 2 ? gelu_bf(z) : gelu_f(z)));
+    }
   }
-  __syncthreads();
-  const int nt = min(TB, T0 - t0);
-  for (int i = threadIdx.x; i < nt * CH; i += 256) {
-    const int tl = i / CH, c = i % CH;
-    const float y = conv_at(xs, ws, tl, c);
-    const float z = (y - mu[c]) * rs[c] * gamma[c] + beta[c];
-    stf<T>(out + ((long)b * T0 + t0 + tl) * CH + c, (sizeof(T) == 2 ? gelu_bf(z) : gelu_f(z)));
+  if (RAGGED) {
+    const int na = min(TB, T0 - t0);
+    for (int i = nt * CH + threadIdx.x; i < na * CH; i += 256) stf<T>(out + ((long)b * T0 + t0) * CH + i, 0.f);
   }
 }
 
 // backward pass 1: per (b,c) A = sum_t dz*yhat, Bs = sum_t dz   (dz = dout * gelu'(z))
-template <typename T>
+// RAGGED: over the clip's own frames; a time block wholly past them adds nothing and reads nothing
+template <typename T, bool RAGGED>
 __global__ __launch_bounds__(256) void conv0_bwd_stats(const float* __restrict__ x, const float* __restrict__ w, long S,
                                                        int T0, const float* __restrict__ stats,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       float eps, const T* __restrict__ dout, float* __restrict__ red) {
+                                                       float eps, const T* __restrict__ dout, float* __restrict__ red,
+                                                       const int64_t* __restrict__ len) {
   __shared__ float xs[TB * KS + KW];
   __shared__ float ws[CH * KW];
   const int b = blockIdx.y, t0 = blockIdx.x * TB;
-  stage(x, w, S, b, t0, xs, ws);
-  const int nt = min(TB, T0 - t0);
+  const long n = RAGGED ? clip_samples(len, b, S) : S;
+  const int Tb = RAGGED ? clip_frames(n, T0) : T0;
+  if (RAGGED && t0 >= Tb) return;
+  stage(x, w, S, n, b, t0, xs, ws);
+  const int nt = min(TB, Tb - t0);
   for (int c = threadIdx.x; c < CH; c += 256) {
     const float s = stats[((long)b * CH + c) * 2], q = stats[((long)b * CH + c) * 2 + 1];
-    const float m = s / T0, r = rsqrtf(fmaxf(q / T0 - m * m, 0.f) + eps);
+    const float m = s / Tb, r = rsqrtf(fmaxf(q / Tb - m * m, 0.f) + eps);
     float A = 0.f, Bs = 0.f;
     for (int tl = 0; tl < nt; ++tl) {
       const float yh = (conv_at(xs, ws, tl, c) - m) * r;
@@ -128,18 +166,22 @@ __global__ __launch_bounds__(256) void conv0_bwd_stats(const float* __restrict__
 }
 
 // backward pass 2: dy = rstd*(gamma*dz - gamma*Bs/T0 - yhat*gamma*A/T0);  dw[c,k] += sum_t dy x[5t+k]
-template <typename T>
+// RAGGED: T0_b in T0's place (the sweep ends at the clip's last own time block; a workgroup with no block of the
+// clip writes a zero slab row)
+template <typename T, bool RAGGED>
 __global__ __launch_bounds__(256) void conv0_bwd_dw(const float* __restrict__ x, const float* __restrict__ w, long S,
                                                     int T0, const float* __restrict__ stats,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     float eps, const T* __restrict__ dout, const float* __restrict__ red,
-                                                    float* __restrict__ part) {
+                                                    float* __restrict__ part, const int64_t* __restrict__ len) {
   // each workgroup sweeps a strided set of time blocks and keeps its dw partials in registers, then writes
   // them once to its slab row (four workgroups per CU: the recompute of conv + GroupNorm + GELU' is VALU work
   // that one wave per SIMD left latency-bound)
   __shared__ float xs[TB * KS + KW];
   __shared__ float ws[CH * KW];
   const int b = blockIdx.y;
+  const long n = RAGGED ? clip_samples(len, b, S) : S;
+  const int Tb = RAGGED ? clip_frames(n, T0) : T0;
   for (int i = threadIdx.x; i < CH * KW; i += 256) ws[i] = w[i];
   constexpr int CPT = CH / 256;   // channels per thread
   float acc[CPT][KW], m[CPT], r[CPT], g[CPT], be[CPT], A[CPT], Bm[CPT];
@@ -147,23 +189,23 @@ __global__ __launch_bounds__(256) void conv0_bwd_dw(const float* __restrict__ x,
   for (int j = 0; j < CPT; ++j) {
     const int c = threadIdx.x + j * 256;
     const float s = stats[((long)b * CH + c) * 2], q = stats[((long)b * CH + c) * 2 + 1];
-    m[j] = s / T0;
-    r[j] = rsqrtf(fmaxf(q / T0 - m[j] * m[j], 0.f) + eps);
+    m[j] = s / Tb;
+    r[j] = rsqrtf(fmaxf(q / Tb - m[j] * m[j], 0.f) + eps);
     g[j] = gamma[c];
     be[j] = beta[c];
-    A[j] = red[((long)b * CH + c) * 2] * g[j] / T0;
-    Bm[j] = red[((long)b * CH + c) * 2 + 1] * g[j] / T0;
+    A[j] = red[((long)b * CH + c) * 2] * g[j] / Tb;
+    Bm[j] = red[((long)b * CH + c) * 2 + 1] * g[j] / Tb;
 #pragma unroll
     for (int k = 0; k < KW; ++k) acc[j][k] = 0.f;
   }
-  const int ntb = (T0 + TB - 1) / TB;
+  const int ntb = (Tb + TB - 1) / TB;
   for (int tb = blockIdx.x; tb < ntb; tb += gridDim.x) {
     const int t0 = tb * TB;
     __syncthreads();
     const long base = (long)b * S + (long)t0 * KS;
-    for (int i = threadIdx.x; i < TB * KS + KW; i += 256) xs[i] = ((long)t0 * KS + i < S) ? x[base + i] : 0.f;
+    for (int i = threadIdx.x; i < TB * KS + KW; i += 256) xs[i] = ((long)t0 * KS + i < n) ? x[base + i] : 0.f;
     __syncthreads();
-    const int nt = min(TB, T0 - t0);
+    const int nt = min(TB, Tb - t0);
     for (int tl = 0; tl < nt; ++tl) {
 #pragma unroll
       for (int j = 0; j < CPT; ++j) {
@@ -232,21 +274,62 @@ extern "C" int64_t dfk_w2v_conv0_fwd_workspace(int64_t B, int64_t S) {
   return (int64_t)4 * B * dfk_cdiv(T0, TB) * CH * 2;
 }
 
+namespace {
+
+template <bool RAGGED>
+void conv0_fwd_launch(const float* wave, int64_t B, int64_t S, const float* w, const float* gamma, const float* beta,
+                      float eps, float* stats, void* out, int dtype, float* ws, const int64_t* len, hipStream_t s) {
+  const int T0 = (int)((S - KW) / KS + 1);
+  const dim3 grid(dfk_cdiv(T0, TB), (unsigned)B);
+  static_assert((CH * 2) % 64 == 0, "stats columns per workgroup");
+  hipLaunchKernelGGL(conv0_stats<RAGGED>, grid, dim3(256), 0, s, wave, w, (long)S, T0, ws, len);
+  hipLaunchKernelGGL(conv0_stats_sum, dim3(CH * 2 / 64, (unsigned)B), dim3(256), 0, s, ws, (int)grid.x, stats);
+  if (dtype == DFK_BF16)
+    hipLaunchKernelGGL((conv0_apply<bf16raw, RAGGED>), grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta,
+                       eps, (bf16raw*)out, len);
+  else
+    hipLaunchKernelGGL((conv0_apply<float, RAGGED>), grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta,
+                       eps, (float*)out, len);
+}
+
+template <bool RAGGED>
+void conv0_bwd_launch(const float* wave, int64_t B, int64_t S, const float* w, const float* gamma, const float* beta,
+                      float eps, const float* stats, const void* dout, int dtype, float* scratch, float* dw,
+                      float* dgamma, float* dbeta, const int64_t* len, hipStream_t s) {
+  const int T0 = (int)((S - KW) / KS + 1);
+  const dim3 grid(dfk_cdiv(T0, TB), (unsigned)B);
+  const dim3 gdw(conv0_dw_blocks(B, T0), (unsigned)B);
+  float* part = scratch + B * CH * 2;   // [B * gdw.x][CH * KW] slab after the [B, CH, 2] reductions
+  (void)hipMemsetAsync(scratch, 0, sizeof(float) * B * CH * 2, s);
+  if (dtype == DFK_BF16) {
+    hipLaunchKernelGGL((conv0_bwd_stats<bf16raw, RAGGED>), grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma,
+                       beta, eps, (const bf16raw*)dout, scratch, len);
+    hipLaunchKernelGGL((conv0_bwd_dw<bf16raw, RAGGED>), gdw, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta,
+                       eps, (const bf16raw*)dout, scratch, part, len);
+  } else {
+    hipLaunchKernelGGL((conv0_bwd_stats<float, RAGGED>), grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma,
+                       beta, eps, (const float*)dout, scratch, len);
+    hipLaunchKernelGGL((conv0_bwd_dw<float, RAGGED>), gdw, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta,
+                       eps, (const float*)dout, scratch, part, len);
+  }
+  hipLaunchKernelGGL(dw_slab_sum, dim3(dfk_cdiv(CH * KW, 64), dfk_cdiv(B * gdw.x, 128)), dim3(256), 0, s, part,
+                     (int)(B * gdw.x), dw);
+  if (dgamma || dbeta)
+    hipLaunchKernelGGL(gn_affine_grad, dim3(dfk_cdiv(CH, 256)), dim3(256), 0, s, scratch, (int)B, dgamma, dbeta);
+}
+
+// the argument rules of the ragged entry points: B is a grid dimension, T0 an int
+bool conv0_ragged_shape_ok(int64_t B, int64_t S, int dtype) {
+  return B > 0 && B <= 65535 && S >= KW && S <= ((int64_t)1 << 31) && (dtype == DFK_F32 || dtype == DFK_BF16);
+}
+
+}  // namespace
+
 extern "C" int dfk_w2v_conv0_fwd(const float* wave, int64_t B, int64_t S, const float* w, const float* gamma,
                                  const float* beta, float eps, float* stats, void* out, int dtype, float* ws,
                                  hipStream_t s) {
   if (!wave || !w || !gamma || !beta || !stats || !out || !ws || S < KW) return DFK_EINVAL;
-  const int T0 = (int)((S - KW) / KS + 1);
-  const dim3 grid(dfk_cdiv(T0, TB), (unsigned)B);
-  static_assert((CH * 2) % 64 == 0, "stats columns per workgroup");
-  hipLaunchKernelGGL(conv0_stats, grid, dim3(256), 0, s, wave, w, (long)S, T0, ws);
-  hipLaunchKernelGGL(conv0_stats_sum, dim3(CH * 2 / 64, (unsigned)B), dim3(256), 0, s, ws, (int)grid.x, stats);
-  if (dtype == DFK_BF16)
-    hipLaunchKernelGGL(conv0_apply<bf16raw>, grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta, eps,
-                       (bf16raw*)out);
-  else
-    hipLaunchKernelGGL(conv0_apply<float>, grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta, eps,
-                       (float*)out);
+  conv0_fwd_launch<false>(wave, B, S, w, gamma, beta, eps, stats, out, dtype, ws, nullptr, s);
   DFK_CHECK_LAUNCH();
   return 0;
 }
@@ -257,26 +340,29 @@ extern "C" int dfk_w2v_conv0_bwd(const float* wave, int64_t B, int64_t S, const 
                                  hipStream_t s) {
   if (!wave || !w || !gamma || !beta || !stats || !dout || !scratch || !dw || S < KW) return DFK_EINVAL;
   if (scratch_bytes < dfk_w2v_conv0_bwd_workspace(B, S)) return DFK_EINVAL;   // the dw slab is sized per launch
-  const int T0 = (int)((S - KW) / KS + 1);
-  const dim3 grid(dfk_cdiv(T0, TB), (unsigned)B);
-  const dim3 gdw(conv0_dw_blocks(B, T0), (unsigned)B);
-  float* part = scratch + B * CH * 2;   // [B * gdw.x][CH * KW] slab after the [B, CH, 2] reductions
-  (void)hipMemsetAsync(scratch, 0, sizeof(float) * B * CH * 2, s);
-  if (dtype == DFK_BF16) {
-    hipLaunchKernelGGL(conv0_bwd_stats<bf16raw>, grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta, eps,
-                       (const bf16raw*)dout, scratch);
-    hipLaunchKernelGGL(conv0_bwd_dw<bf16raw>, gdw, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta, eps,
-                       (const bf16raw*)dout, scratch, part);
-  } else {
-    hipLaunchKernelGGL(conv0_bwd_stats<float>, grid, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta, eps,
-                       (const float*)dout, scratch);
-    hipLaunchKernelGGL(conv0_bwd_dw<float>, gdw, dim3(256), 0, s, wave, w, (long)S, T0, stats, gamma, beta, eps,
-                       (const float*)dout, scratch, part);
-  }
-  hipLaunchKernelGGL(dw_slab_sum, dim3(dfk_cdiv(CH * KW, 64), dfk_cdiv(B * gdw.x, 128)), dim3(256), 0, s, part,
-                     (int)(B * gdw.x), dw);
-  if (dgamma || dbeta)
-    hipLaunchKernelGGL(gn_affine_grad, dim3(dfk_cdiv(CH, 256)), dim3(256), 0, s, scratch, (int)B, dgamma, dbeta);
+  conv0_bwd_launch<false>(wave, B, S, w, gamma, beta, eps, stats, dout, dtype, scratch, dw, dgamma, dbeta, nullptr, s);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_w2v_conv0_ragged_fwd(const float* wave, int64_t B, int64_t S, const float* w, const float* gamma,
+                                        const float* beta, float eps, float* stats, void* out, int dtype, float* ws,
+                                        const int64_t* len, hipStream_t s) {
+  if (!wave || !w || !gamma || !beta || !stats || !out || !ws || !len) return DFK_EINVAL;
+  if (!conv0_ragged_shape_ok(B, S, dtype)) return DFK_EINVAL;
+  conv0_fwd_launch<true>(wave, B, S, w, gamma, beta, eps, stats, out, dtype, ws, len, s);
+  DFK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfk_w2v_conv0_ragged_bwd(const float* wave, int64_t B, int64_t S, const float* w, const float* gamma,
+                                        const float* beta, float eps, const float* stats, const void* dout, int dtype,
+                                        float* scratch, int64_t scratch_bytes, float* dw, float* dgamma, float* dbeta,
+                                        const int64_t* len, hipStream_t s) {
+  if (!wave || !w || !gamma || !beta || !stats || !dout || !scratch || !dw || !len) return DFK_EINVAL;
+  if (!conv0_ragged_shape_ok(B, S, dtype)) return DFK_EINVAL;
+  if (scratch_bytes < dfk_w2v_conv0_bwd_workspace(B, S)) return DFK_EINVAL;   // the dw slab is sized per launch
+  conv0_bwd_launch<true>(wave, B, S, w, gamma, beta, eps, stats, dout, dtype, scratch, dw, dgamma, dbeta, len, s);
   DFK_CHECK_LAUNCH();
   return 0;
 }

@@ -549,26 +549,27 @@ class RowMeanFn(torch.autograd.Function):
 
 class W2VConv0Fn(torch.autograd.Function):
     """wav2vec2 conv layer 0: Conv1d(1->512,k10,s5) + GroupNorm(512,512) + GELU
-    (HF modeling_wav2vec2.py:302-323) -> channels-last [B, T0, 512]."""
+    (HF modeling_wav2vec2.py:302-323) -> channels-last [B, T0, 512].  lengths (device int64 [B], padded batches):
+    each clip's GroupNorm over its own frames, zero rows behind them (K.w2v_conv0_fwd)."""
 
     @staticmethod
-    def forward(ctx, wave, weight, gamma, beta, eps, dtype):
+    def forward(ctx, wave, weight, gamma, beta, eps, dtype, lengths=None):
         w = weight.detach().float().reshape(512, 10).contiguous()
         out, stats = K.w2v_conv0_fwd(wave.float().contiguous(), w, gamma.detach().float(), beta.detach().float(), eps,
-                                     dtype)
+                                     dtype, lengths)
         for i, p in enumerate((weight, gamma, beta)):
             grad_use(ctx, 1 + i, p)
-        ctx.save_for_backward(wave, w, weight, gamma, beta, stats)
+        ctx.save_for_backward(wave, w, weight, gamma, beta, stats, *(() if lengths is None else (lengths,)))
         ctx.eps = eps
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        wave, w, weight, gamma, beta, stats = ctx.saved_tensors
+        wave, w, weight, gamma, beta, stats, *lengths = ctx.saved_tensors
         dw, dg, db = grad_sink(weight), grad_sink(gamma), grad_sink(beta)
         K.w2v_conv0_bwd(wave.float().contiguous(), w, gamma.detach().float(), beta.detach().float(), ctx.eps, stats,
-                        dout.contiguous(), dw.view(512, 10), dg, db)
-        return None, grad_done(weight, dw), grad_done(gamma, dg), grad_done(beta, db), None, None
+                        dout.contiguous(), dw.view(512, 10), dg, db, lengths[0] if lengths else None)
+        return None, grad_done(weight, dw), grad_done(gamma, dg), grad_done(beta, db), None, None, None
 
 
 def _conv1d_gemm_fwd(x, weight, stride, out, bias=None, act=0, aux=None):

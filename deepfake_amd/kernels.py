@@ -593,21 +593,35 @@ def rowmean_ragged_bwd(dy, flen, T, dtype):
     return dx
 
 
-def w2v_conv0_fwd(wave, w, gamma, beta, eps, dtype):
+def w2v_conv0_fwd(wave, w, gamma, beta, eps, dtype, lengths=None):
+    """lengths (device int64 [B], clamped by the kernels): the GroupNorm statistics of each clip over its own
+    frames, the samples past its length never read, the rows past its frames written as zero."""
     B, S = wave.shape
     T0 = (S - 10) // 5 + 1
     out = torch.empty(B, T0, 512, device=wave.device, dtype=dtype)
     stats = torch.empty(B, 512, 2, device=wave.device, dtype=torch.float32)
     ws = torch.empty(max(L.lib().dfk_w2v_conv0_fwd_workspace(B, S) // 4, 1), device=wave.device, dtype=torch.float32)
+    if lengths is not None:
+        L.check(L.lib().dfk_w2v_conv0_ragged_fwd(L.ptr(wave), B, S, L.ptr(w), L.ptr(gamma), L.ptr(beta), float(eps),
+                                                 L.ptr(stats), L.ptr(out), L.dt(out), L.ptr(ws), _flen(lengths, B),
+                                                 L.stream()), "w2v_conv0_ragged_fwd")
+        return out, stats
     L.check(L.lib().dfk_w2v_conv0_fwd(L.ptr(wave), B, S, L.ptr(w), L.ptr(gamma), L.ptr(beta), float(eps),
                                       L.ptr(stats), L.ptr(out), L.dt(out), L.ptr(ws), L.stream()), "w2v_conv0_fwd")
     return out, stats
 
 
-def w2v_conv0_bwd(wave, w, gamma, beta, eps, stats, dout, dw, dgamma, dbeta):
+def w2v_conv0_bwd(wave, w, gamma, beta, eps, stats, dout, dw, dgamma, dbeta, lengths=None):
+    """dw, dgamma, dbeta +=.  lengths: as the forward's; the rows of dout past a clip's frames are never read."""
     B, S = wave.shape
     scratch = torch.empty(max(L.lib().dfk_w2v_conv0_bwd_workspace(B, S) // 4, B * 512 * 2), device=wave.device,
                           dtype=torch.float32)
+    if lengths is not None:
+        L.check(L.lib().dfk_w2v_conv0_ragged_bwd(L.ptr(wave), B, S, L.ptr(w), L.ptr(gamma), L.ptr(beta), float(eps),
+                                                 L.ptr(stats), L.ptr(dout), L.dt(dout), L.ptr(scratch),
+                                                 scratch.numel() * 4, L.ptr(dw), L.ptr(dgamma), L.ptr(dbeta),
+                                                 _flen(lengths, B), L.stream()), "w2v_conv0_ragged_bwd")
+        return
     L.check(L.lib().dfk_w2v_conv0_bwd(L.ptr(wave), B, S, L.ptr(w), L.ptr(gamma), L.ptr(beta), float(eps),
                                       L.ptr(stats), L.ptr(dout), L.dt(dout), L.ptr(scratch),
                                       scratch.numel() * 4, L.ptr(dw), L.ptr(dgamma),

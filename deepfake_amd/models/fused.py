@@ -17,7 +17,7 @@ from .audioTransformer import Audio2D
 from .ModalFusion import FusionModel
 from .swin_transformer2d import SwinTransformerV2
 from .video_swin_transformer import SwinTransformer3D, VSTFeat
-from .wav2vec2 import Wav2Vec2Config, Wav2Vec2Model
+from .wav2vec2 import Wav2Vec2Config, Wav2Vec2Model, padded_batches
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 W2V_CONFIG = os.path.join(HERE, "w2v_base_config.json")
@@ -51,11 +51,13 @@ def _w2v_config_path(args, default=W2V_CONFIG):
 
 
 def check_paudio_lengths(args, wcfg):
-    """--paudio_lengths needs the layer-norm / pre-norm family (the group-norm conv0 runs over the whole padded row):
-    fail at start-up, not at the first batch."""
-    if getattr(args, "paudio_lengths", False) and not (wcfg.feat_extract_norm == "layer" and wcfg.do_stable_layer_norm):
+    """--paudio_lengths needs the layer-norm / pre-norm family, or the group-norm family with masked_group_norm (the
+    plain group-norm conv0 runs over the whole padded row): fail at start-up, not at the first batch."""
+    if getattr(args, "paudio_lengths", False) and not padded_batches(wcfg):
         raise ValueError("--paudio_lengths needs a layer-norm --w2v_config (e.g. deepfake_amd/models/"
-                         "w2v_large_config.json); the wav2vec2-base family has no padded-batch path")
+                         "w2v_large_config.json) or the wav2vec2-base one with per-clip GroupNorm statistics "
+                         "(deepfake_amd/models/w2v_base_masked_config.json); the plain wav2vec2-base config has no "
+                         "padded-batch path")
 
 
 def build_fused(cfg, args=None, w2v_config=None, compute_dtype=torch.float32, regularize=False, fp8=False):

@@ -28,11 +28,15 @@ discarded (torch.where), its gradients are zero and the fused SGD skips its
 parameters (as torch's SGD skips grad=None).  config.deterministic() turns all
 of them off (the parity setting, Q12).
 
-Padded batches (layer-norm family only): Wav2Vec2Model.forward(wave, lengths=n) gives every clip the result it
-would get alone — frame_lengths() turns the sample counts into frame counts on the device, the hidden states past a
-clip's frames are zeroed before the positional conv and after the encoder's final LayerNorm (Fn.RowMaskFn), every
-layer's attention masks the keys past them (klen), and SpecAugment draws its spans inside them.  The lengths are
-never read on the host, so the step stays capturable.
+Padded batches: Wav2Vec2Model.forward(wave, lengths=n) gives every clip the result it would get alone —
+frame_lengths() turns the sample counts into frame counts on the device, the hidden states past a clip's frames are
+zeroed before the positional conv and after the encoder (Fn.RowMaskFn), every layer's attention masks the keys past
+them (klen), and SpecAugment draws its spans inside them.  The lengths are never read on the host, so the step stays
+capturable.  The layer-norm family takes lengths= as it is.  The group-norm family needs config.masked_group_norm
+(w2v_base_masked_config.json; not an HF field): conv0's GroupNorm then takes each channel's mean and variance over
+the clip's own frames (dfk_w2v_conv0_ragged_*), which is HF's arithmetic on the clip alone and not HF's on the padded
+batch, where the padding enters every frame's statistics and no attention mask undoes it.  Without the field
+lengths= raises on that family.
 """
 import json
 
@@ -69,6 +73,12 @@ class Wav2Vec2Config:
         self.mask_feature_prob = kw.get("mask_feature_prob", 0.0)
         self.apply_spec_augment = kw.get("apply_spec_augment", True)
         self.layerdrop = kw.get("layerdrop", 0.1)
+        # not an HF field: lengths= on the group-norm family, conv0's GroupNorm over each clip's own frames
+        self.masked_group_norm = bool(kw.get("masked_group_norm", False))
+        if self.masked_group_norm and self.feat_extract_norm != "group":
+            raise ValueError(f"masked_group_norm with feat_extract_norm={self.feat_extract_norm!r}: the field selects "
+                             'the padded-batch GroupNorm of feat_extract_norm="group" (the layer-norm family takes '
+                             "lengths= without it)")
         for k in ("hidden_dropout", "attention_dropout", "activation_dropout", "feat_proj_dropout"):
             setattr(self, k, kw.get(k, 0.1))
 
@@ -96,6 +106,14 @@ def frame_lengths(n, config):
     for k, s in zip(config.conv_kernel, config.conv_stride):
         n = torch.div(n - k, s, rounding_mode="floor") + 1 if torch.is_tensor(n) else (n - k) // s + 1
     return n
+
+
+def padded_batches(config):
+    """Whether the config has a padded-batch path (lengths=): the layer-norm / pre-norm family, or the group-norm
+    family with masked_group_norm."""
+    if config.feat_extract_norm == "layer":
+        return bool(config.do_stable_layer_norm)
+    return config.feat_extract_norm == "group" and bool(getattr(config, "masked_group_norm", False))
 
 
 def receptive_field(config):
@@ -149,8 +167,11 @@ class Wav2Vec2FeatureEncoder(nn.Module):
                 for i in range(len(config.conv_dim))])
         self.compute_dtype = torch.float32
 
-    def forward(self, input_values):
-        """[B, S] fp32 -> channels-last [B, T, 512] (compute dtype)."""
+    def forward(self, input_values, lengths=None):
+        """[B, S] fp32 -> channels-last [B, T, 512] (compute dtype).  lengths (device int64 [B], group path): conv0
+        over each clip's own samples and frames, zero rows behind them; conv1..6 carry no bias and gelu(0) = 0, so
+        the frames that see padding only stay zero, and those that straddle a clip's end lie at or past its frame
+        count, where the encoder's row mask removes them."""
         l0 = self.conv_layers[0]
         if self.layer_norm_path:
             x = Fn.W2VConv0LNFn.apply(input_values, l0.conv.weight, l0.conv.bias, l0.layer_norm.weight,
@@ -159,8 +180,12 @@ class Wav2Vec2FeatureEncoder(nn.Module):
                 x = Fn.ConvLNGeluFn.apply(x, layer.conv.weight, layer.conv.bias, layer.layer_norm.weight,
                                           layer.layer_norm.bias, layer.stride, layer.layer_norm.eps)
             return x
-        x = Fn.W2VConv0Fn.apply(input_values, l0.conv.weight, l0.layer_norm.weight, l0.layer_norm.bias,
-                                l0.layer_norm.eps, self.compute_dtype)
+        if lengths is None:
+            x = Fn.W2VConv0Fn.apply(input_values, l0.conv.weight, l0.layer_norm.weight, l0.layer_norm.bias,
+                                    l0.layer_norm.eps, self.compute_dtype)
+        else:
+            x = Fn.W2VConv0Fn.apply(input_values, l0.conv.weight, l0.layer_norm.weight, l0.layer_norm.bias,
+                                    l0.layer_norm.eps, self.compute_dtype, lengths)
         for layer in self.conv_layers[1:]:
             x = Fn.ConvGeluFn.apply(x, layer.conv.weight, layer.stride)
         return x
@@ -263,11 +288,11 @@ class Wav2Vec2EncoderLayer(nn.Module):
         self.feed_forward = Wav2Vec2FeedForward(config)
         self.final_layer_norm = nn.LayerNorm(config.hidden_size, eps=config.layer_norm_eps)
 
-    def forward(self, x, B, T):
+    def forward(self, x, B, T, klen=None):
         tr = self.training
         ff = self.feed_forward
         spec = lambda d: d.spec() if d.active(tr) else None   # noqa: E731
-        a, xs = self.attention.core(x, B, T, skip=True)
+        a, xs = self.attention.core(x, B, T, skip=True, klen=klen)
         x = Fn.layer_norm(Fn.linear(a, self.attention.out_proj.weight, self.attention.out_proj.bias, residual=xs,
                                     drop=spec(self.dropout)), self.layer_norm)
         x = Fn.mlp(x, ff.intermediate_dense, ff.output_dense, residual=x, drop_act=spec(ff.intermediate_dropout),
@@ -276,7 +301,9 @@ class Wav2Vec2EncoderLayer(nn.Module):
 
 
 class Wav2Vec2Encoder(nn.Module):
-    """HF/:657-727 (no attention mask: equal-length clips, Q13)."""
+    """HF/:657-727.  flen (device int64 [B], padded batches): the frames past a clip's own are zeroed before the
+    positional conv (HF/:678-681), every layer's attention masks them as keys, and the output's rows there are
+    zeroed (HF leaves the last LayerNorm's output in them)."""
 
     layer_class = Wav2Vec2EncoderLayer
 
@@ -310,14 +337,19 @@ class Wav2Vec2Encoder(nn.Module):
         """Called with zero_grad (ParamStore.zero_gates): a new accumulation window starts with no layer kept."""
         self.layer_used.zero_()
 
-    def forward(self, h):
+    def forward(self, h, flen=None):
         B, T, C = h.shape
+        klen = None
+        if flen is not None:
+            h = Fn.RowMaskFn.apply(h, flen)
+            klen = flen.clamp(1, T).to(torch.int32)
         d = self.dropout.spec() if self.dropout.active(self.training) else None
         x = Fn.layer_norm(self.pos_conv_embed.add_to(h.contiguous()), self.layer_norm, drop=d).reshape(B * T, C)
-        return self._run_layers(x, B, T).view(B, T, C)
+        y = self._run_layers(x, B, T, klen).view(B, T, C)
+        return y if flen is None else Fn.RowMaskFn.apply(y, flen)
 
     def _run_layers(self, x, B, T, klen=None):
-        """The layers on x [B*T, C] under LayerDrop (HF/:700-706); klen: the pre-LN layers' key lengths."""
+        """The layers on x [B*T, C] under LayerDrop (HF/:700-706); klen: the layers' key lengths."""
         lds = self.layerdrop.active(self.training)
         if lds:
             K.layerdrop_flags(self.layerdrop.spec(), self.layer_keep, self.layer_used)
@@ -375,8 +407,8 @@ class Wav2Vec2EncoderStableLayerNorm(Wav2Vec2Encoder):
 class Wav2Vec2Model(nn.Module):
     """HF/:1244-1380 forward.  config.do_stable_layer_norm picks the encoder (HF/:1255) and
     config.feat_extract_norm the feature encoder.  Padded batches come with lengths= (the samples of each clip, an
-    int64 [B] device tensor that is never read on the host, or host integers, which are validated), layer-norm
-    family only; HF's attention_mask argument raises."""
+    int64 [B] device tensor that is never read on the host, or host integers, which are validated): the layer-norm
+    family, and the group-norm family with config.masked_group_norm; HF's attention_mask argument raises."""
 
     def __init__(self, config):
         super().__init__()
@@ -407,9 +439,10 @@ class Wav2Vec2Model(nn.Module):
         """lengths= of forward() as an int64 [B] tensor on the waveform's device.  A device tensor is checked for
         shape and dtype only (its values are clamped by the kernels that read them); host integers must lie in
         [receptive field, S]."""
-        if not (self.config.feat_extract_norm == "layer" and self.config.do_stable_layer_norm):
+        if not padded_batches(self.config):
             raise NotImplementedError("lengths= (padded batches) with the group-norm / post-LN family: its conv0 "
-                                      "GroupNorm runs over the whole padded row")
+                                      "GroupNorm runs over the whole padded row (masked_group_norm in the config "
+                                      "selects the per-clip statistics)")
         B, S = input_values.shape
         if torch.is_tensor(lengths) and lengths.is_cuda:
             if lengths.dtype != torch.int64 or lengths.shape != (B,):
@@ -430,8 +463,12 @@ class Wav2Vec2Model(nn.Module):
             raise NotImplementedError("attention_mask (padded batches): pass lengths=")
         flen = None
         if lengths is not None:
-            flen = frame_lengths(self.sample_lengths(input_values, lengths), self.config)
-        f = self.feature_extractor(input_values)
+            lengths = self.sample_lengths(input_values, lengths)
+            flen = frame_lengths(lengths, self.config)
+        if lengths is not None and not self.feature_extractor.layer_norm_path:
+            f = self.feature_extractor(input_values, lengths)
+        else:   # the layer-norm conv stack is per frame: its padded frames are removed by the encoder's row mask
+            f = self.feature_extractor(input_values)
         h, ext = self.feature_projection(f)
         h = self._mask_hidden_states(h, flen)
         h = self.encoder(h) if flen is None else self.encoder(h, flen)

@@ -335,6 +335,22 @@ int dfk_w2v_conv0_bwd(const float* wave, int64_t B, int64_t S, const float* w, c
                       const float* beta, float eps, const float* stats, const void* dout, int dtype,
                       float* scratch, int64_t scratch_bytes, float* dw, float* dgamma, float* dbeta,
                       hipStream_t stream);
+/* Padded batches (Wav2Vec2Config.masked_group_norm): the two calls above with len, int64 [B] on the device and
+ * read there only.  Clip b holds n_b = clamp(len[b], 1, S) samples of its row and T0_b = clamp((n_b-10)/5+1, 1, T0)
+ * frames.  Samples at or past n_b are taken as zero and never loaded; the GroupNorm sum, sum of squares (stats)
+ * and their divisor run over the frames t < T0_b, so these frames are what the clip gives alone; the rows
+ * T0_b <= t < T0 of out are written as 0.  Backward: the reductions and dw run over t < T0_b with T0_b as the
+ * divisor, and the rows >= T0_b of dout are never read.  With every length full the forward is bitwise the
+ * uniform call's.  ws / scratch are sized by the workspace functions above.  DFK_EINVAL before any launch for a
+ * NULL operand (len included; dgamma / dbeta may be NULL), B <= 0 or > 65535, S < 10 or > 2^31, a dtype other
+ * than DFK_F32 / DFK_BF16, a short scratch. */
+int dfk_w2v_conv0_ragged_fwd(const float* wave, int64_t B, int64_t S, const float* w, const float* gamma,
+                             const float* beta, float eps, float* stats, void* out, int dtype, float* ws,
+                             const int64_t* len, hipStream_t stream);
+int dfk_w2v_conv0_ragged_bwd(const float* wave, int64_t B, int64_t S, const float* w, const float* gamma,
+                             const float* beta, float eps, const float* stats, const void* dout, int dtype,
+                             float* scratch, int64_t scratch_bytes, float* dw, float* dgamma, float* dbeta,
+                             const int64_t* len, hipStream_t stream);
 
 /* wav2vec2 layer-norm feature encoder (HF modeling_wav2vec2.py:275-299, Wav2Vec2LayerNormConvLayer, all seven
  * conv layers when feat_extract_norm == "layer"): conv (+ bias) -> LayerNorm over the 512 channels of each frame

@@ -1,6 +1,6 @@
 // Host-side checks of libdfk under AddressSanitizer (CPU only; no kernel is launched).  Exercises the C ABI's
 // host code: workspace planners (GEMM split-K, attention table / backward scratch, LayerNorm slab, wav2vec2
-// conv0 on both the group-norm and the layer-norm path, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
+// conv0 on both the group-norm (with and without per-clip lengths) and the layer-norm path, mel with and without the resampler), argument validation on malformed inputs (null pointers, bad strides / shapes, unsupported head
 // dims, the SGD and AdamW entry points' buffers / run table / hyper-parameters, the gradient-clipping entry points' slab /
 // coefficient / max_norm / run table, the parameter-group entry points' map / pairs / group count, the weight-EMA entry points' buffers / decay), which must return DFK_EINVAL before touching
 // the device.  Built and run by tools/asan/run.sh.
@@ -513,6 +513,63 @@ int main() {
     EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vodd, DFK_BF16, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
     EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vx, DFK_BF16, odd, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
     EXPECT(dfk_w2v_ln_gelu_bwd(vx, vx, 100, 512, fx, fx, fx, vx, 9, fx, ws1, fx, fx, fx, nullptr) == DFK_EINVAL);
+  }
+  {
+    // wav2vec2 group-norm conv0 with per-clip lengths: null operands (the lengths included), B <= 0 or past the
+    // grid, S < 10, a bad dtype, a short scratch: all before any launch
+    float* fx = reinterpret_cast<float*>(0x10000);
+    void* vx = reinterpret_cast<void*>(0x20000);
+    const int64_t* ln = reinterpret_cast<const int64_t*>(0x30000);
+    const int64_t ws0 = dfk_w2v_conv0_bwd_workspace(8, 64000);
+    EXPECT(ws0 > 0);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(nullptr, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, nullptr, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, nullptr, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, fx, nullptr, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, fx, fx, 1e-5f, nullptr, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, nullptr, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, nullptr, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 0, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, -1, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 65536, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 9, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, ((int64_t)1 << 31) + 1, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, 7, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_fwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, -1, fx, ln, nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(nullptr, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, nullptr, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, nullptr, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, nullptr, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, nullptr, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, nullptr, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, nullptr, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, nullptr, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);                                                    // no dw sink
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, nullptr, nullptr) ==
+           DFK_EINVAL);                                                    // no lengths
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0 - 1, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);                                                    // short scratch
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, 0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 0, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, -3, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 65536, 64000, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, INT64_MAX, fx, fx, fx, ln,
+                                    nullptr) == DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 5, fx, fx, fx, 1e-5f, fx, vx, DFK_BF16, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
+    EXPECT(dfk_w2v_conv0_ragged_bwd(fx, 8, 64000, fx, fx, fx, 1e-5f, fx, vx, 2, fx, ws0, fx, fx, fx, ln, nullptr) ==
+           DFK_EINVAL);
   }
   EXPECT(dfk_cpb_bias_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 169, 512, 64, nullptr) != 0);
   std::printf("host_check: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);
